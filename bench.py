@@ -238,6 +238,41 @@ def exchange_selftest(world, rank, workload="cfg2"):
     return 0 if ok else 1
 
 
+DUMP_SAMPLES = 1 << 20  # entries of each sampled array of --dump-outputs (4 MB of float32 apiece)
+DUMP_SEED = 1234
+
+
+def dump_outputs(path, torch, enc, errcs, out):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy, so that two builds can be compared
+    output for output (about 9 MB at 4096 frames):
+      jls_sizes, encode_errcs, decode_errcs     per frame, float64
+      jls_byte_sums, decoded_sample_sums        per frame, float64: the sum of the bytes of its .jls / of its decoded samples
+      jls_bytes_sample                          float32: DUMP_SAMPLES (frame, offset) pairs drawn with DUMP_SEED over the
+                                                stream slots, -1 where the offset lies past that frame's .jls
+      decoded_sample                            float32: DUMP_SAMPLES (frame, sample) pairs drawn with DUMP_SEED over the
+                                                decoded frames
+    The positions depend on the shapes alone: the same arguments draw the same ones in every run."""
+    os.makedirs(path, exist_ok=True)
+    count, pitch = enc.streams.shape
+    dev = enc.streams.device
+    sizes = enc.sizes.astype(np.int64)
+    flat = out.view(count, -1)
+    byte_sums = torch.stack([enc.streams[f, :int(sizes[f])].sum(dtype=torch.int64) for f in range(count)])
+    sample_sums = torch.stack([flat[f].sum(dtype=torch.int64) for f in range(count)])
+    rng = np.random.default_rng(DUMP_SEED)
+    frame, offset = rng.integers(0, count, DUMP_SAMPLES), rng.integers(0, pitch, DUMP_SAMPLES)
+    jls = enc.streams[torch.from_numpy(frame).to(dev), torch.from_numpy(offset).to(dev)].cpu().numpy().astype(np.float32)
+    jls[offset >= sizes[frame]] = -1.0  # (what lies past a stream's end is not output)
+    frame, sample = rng.integers(0, count, DUMP_SAMPLES), rng.integers(0, flat.shape[1], DUMP_SAMPLES)
+    decoded = flat[torch.from_numpy(frame).to(dev), torch.from_numpy(sample).to(dev)].cpu().numpy().astype(np.float32)
+    arrays = {"jls_sizes": sizes.astype(np.float64), "encode_errcs": enc.errcs.astype(np.float64),
+              "decode_errcs": np.asarray(errcs).astype(np.float64), "jls_byte_sums": byte_sums.cpu().numpy().astype(np.float64),
+              "decoded_sample_sums": sample_sums.cpu().numpy().astype(np.float64), "jls_bytes_sample": jls, "decoded_sample": decoded}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"outputs of the last timed step ({count} frames): {', '.join(sorted(arrays))} in {path}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -265,7 +300,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip batch_sweep / data_sweep / single_frame_ms / batch_api_host_buffers / threads_abi")
     ap.add_argument("--selftest-exchange", action="store_true", help="launcher + exchange on fabricated streams (no codec)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller (rank 0's .jls streams and decoded frames: "
+                         "per-frame sizes, error codes and sums, and a fixed seeded sample of bytes and samples) as DIR/<name>.npy, "
+                         "so that two builds can be compared output for output (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_under_torchrun(args))
@@ -403,6 +444,8 @@ def main():
         first = enc.streams[0, :int(enc.sizes[0])].cpu().numpy().tobytes()
         bit_exact = (len(first) == golden["jls_size"] and hashlib.sha256(first).hexdigest() == golden["jls_sha256"])
         assert bit_exact, "frame 0 differs from the reference's .jls (golden hash)"
+    if rank == 0 and args.dump_outputs:  # before the extras: they reuse `frames`, `streams` and `out`
+        dump_outputs(args.dump_outputs, torch, enc, errcs, out)
 
     if rank == 0:
         pixels = WIDTH * HEIGHT

@@ -1,7 +1,9 @@
 """Marker fidelity END TO END on the GPU box: the same C-ABI session -- SPIFF header and directory
 entries, COM, APPn, a mapping table, every encoding option, then a real encode -- is run on libcharls_amd.so and on the
 reference (oracle/_ref/libcharls_ref.so, the checker) and must give the same bytes; the result is decoded by both with
-comment / application-data callbacks, SPIFF and mapping-table queries, and every observation must agree.  Also replays
+comment / application-data callbacks, SPIFF and mapping-table queries, and every observation must agree.  What the
+reference observes is stored in tests/golden/marker_sessions.json, so the comparison holds where oracle/_ref did not
+travel; where it did, the reference is run live as well and must still give what is stored.  Also replays
 tests/abi_scripts.py on the GPU box, where the branches that code a scan really code it.
 
 Reference: src/jpeg_stream_writer.cpp:38-227, src/jpeg_stream_reader.cpp:87-189, test/jpeg_stream_writer_test.cpp,
@@ -22,6 +24,7 @@ from charls_amd.capi import FrameInfo, MappingTableInfo, PcParameters, SpiffHead
 pytestmark = pytest.mark.gpu
 
 REF_PATH = os.path.join(common.ROOT, "oracle", "_ref", "libcharls_ref.so")
+GOLDEN_FILE = os.path.join(common.GOLDEN, "marker_sessions.json")
 
 
 @pytest.fixture(scope="module")
@@ -33,9 +36,15 @@ def lib():
 
 @pytest.fixture(scope="module")
 def ref():
-    if not os.path.exists(REF_PATH):
-        pytest.skip("oracle/_ref/libcharls_ref.so did not travel")
-    return capi.CharLSLibrary(REF_PATH)
+    """The live reference where oracle/_ref travelled, None elsewhere: what it makes of every session here is stored in
+    tests/golden/marker_sessions.json (tests/golden/make_marker_sessions.py) and stands in for it."""
+    return capi.CharLSLibrary(REF_PATH) if os.path.exists(REF_PATH) else None
+
+
+@pytest.fixture(scope="module")
+def golden():
+    with open(GOLDEN_FILE) as f:
+        return json.load(f)
 
 
 def _buf(data: bytes):
@@ -158,36 +167,61 @@ SESSIONS = [
 ]
 
 
-@pytest.mark.parametrize("name,bits,comps,ilv,near,xform,options,table_id,spiff", SESSIONS, ids=[s[0] for s in SESSIONS])
-def test_full_marker_session_matches_the_reference(lib, ref, name, bits, comps, ilv, near, xform, options, table_id, spiff):
-    for w, h in ((37, 23), (64, 40)):  # odd sizes: the even-size option pads some of them
+def session_cases(name, bits, comps, ilv, near, xform, options, table_id, spiff):
+    """(key, image, session arguments) of one row of SESSIONS; odd sizes: the even-size option pads some of them."""
+    for w, h in ((37, 23), (64, 40)):
         img = synth.frame_numpy(w, h, seed=len(name) + w, bits=bits, components=comps, kind="mixed", interleaved=(ilv != 0))
-        kw = dict(bits=bits, comps=comps, ilv=ilv, near=near, xform=xform, options=options, table_id=table_id, spiff=spiff)
-        rc_ref, data_ref = _encode_session(ref, img, **kw)
-        rc_gpu, data_gpu = _encode_session(lib, img, **kw)
-        assert rc_gpu == rc_ref, name
-        assert data_gpu == data_ref, name
+        yield f"{w}x{h}", img, dict(bits=bits, comps=comps, ilv=ilv, near=near, xform=xform, options=options, table_id=table_id,
+                                    spiff=spiff)
+
+
+def observe_session(L, img, **kw):
+    """The encoder session and the decoder session over what it wrote, as stored: (observations, bytes written, samples)."""
+    rc, data = _encode_session(L, img, **kw)
+    obs, px = _decode_session(L, data)
+    return {"rc": rc, "jls_size": len(data), "jls_sha256": common.sha(data), "obs": obs, "px_sha256": common.sha(px)}, data, px
+
+
+TOO_SMALL_IMAGE = dict(width=48, height=31, seed=5, bits=8, kind="mixed")
+TOO_SMALL_SESSION = dict(bits=8, comps=1, ilv=0, near=0, xform=0, options=1 | 2, table_id=2, spiff="standard")
+
+
+def too_small_sizes(full):
+    return (full, full - 1, full - 2, full // 2, 60)
+
+
+def observe_too_small(L, img, size):
+    rc, data = _encode_session(L, img, destination_size=size, **TOO_SMALL_SESSION)
+    return {"rc": rc, "jls_sha256": common.sha(data) if rc[-3] == 0 else None}
+
+
+@pytest.mark.parametrize("name,bits,comps,ilv,near,xform,options,table_id,spiff", SESSIONS, ids=[s[0] for s in SESSIONS])
+def test_full_marker_session_matches_the_reference(lib, ref, golden, name, bits, comps, ilv, near, xform, options, table_id, spiff):
+    for key, img, kw in session_cases(name, bits, comps, ilv, near, xform, options, table_id, spiff):
+        want = golden["sessions"][name][key]
+        if ref is not None:
+            assert observe_session(ref, img, **kw)[0] == want, (name, key)  # the stored observations are still the reference's
+        got, data_gpu, px_gpu = observe_session(lib, img, **kw)
+        for k in ("rc", "jls_size", "jls_sha256", "obs", "px_sha256"):
+            assert got[k] == want[k], (name, key, k)
         if options & 1:
             assert len(data_gpu) % 2 == 0
-        obs_ref, px_ref = _decode_session(ref, data_ref)
-        obs_gpu, px_gpu = _decode_session(lib, data_gpu)
-        assert obs_gpu == obs_ref, name
-        assert px_gpu == px_ref
         if near == 0:
             assert px_gpu == np.ascontiguousarray(img).tobytes()
 
 
-def test_marker_session_with_a_destination_that_is_too_small(lib, ref):
+def test_marker_session_with_a_destination_that_is_too_small(lib, ref, golden):
     """The exact boundary through the whole container: one byte less than the file fails with the reference's code."""
-    img = synth.frame_numpy(48, 31, seed=5, bits=8, kind="mixed")
-    kw = dict(bits=8, comps=1, ilv=0, near=0, xform=0, options=1 | 2, table_id=2, spiff="standard")
-    _, full = _encode_session(ref, img, **kw)
-    for size in (len(full), len(full) - 1, len(full) - 2, len(full) // 2, 60):
-        rc_ref, data_ref = _encode_session(ref, img, destination_size=size, **kw)
-        rc_gpu, data_gpu = _encode_session(lib, img, destination_size=size, **kw)
-        assert rc_gpu == rc_ref, size
-        if rc_ref[-3] == 0:
-            assert data_gpu == data_ref, size
+    img = synth.frame_numpy(**TOO_SMALL_IMAGE)
+    full = golden["too_small"]["full_size"]
+    if ref is not None:
+        assert len(_encode_session(ref, img, **TOO_SMALL_SESSION)[1]) == full
+    sizes = too_small_sizes(full)
+    assert len(golden["too_small"]["observations"]) == len(sizes)
+    for size, want in zip(sizes, golden["too_small"]["observations"]):
+        if ref is not None:
+            assert observe_too_small(ref, img, size) == want, size
+        assert observe_too_small(lib, img, size) == want, size
 
 
 @pytest.mark.parametrize("script", [f.__name__ for f in S.SCRIPTS])
