@@ -512,9 +512,11 @@ void launch_wave_decode(int nc, const ScanDesc* d_descs, ScanResult* d_results, 
 
 uint64_t decode_launch_key(const ScanDesc& d) noexcept
 {
-    // width | components | interleave | wide | eligible : scans with equal keys can share a launch
+    // width | components | interleave | near-lossless | eligible | wide | exact-eligible : scans with equal keys can share a
+    // launch.  The launch picks its kernel from its first scan: a near-lossless scan must not land behind a lossless one (a
+    // 16-bit lossless scan with T3 beyond the group kernel's table takes decode_scans_fast, which has no near-lossless code)
     const uint64_t base = (static_cast<uint64_t>(d.width) << 16) | (static_cast<uint64_t>(d.components & 0xFF) << 8) |
-                          (static_cast<uint64_t>(d.interleave_mode & 3) << 4) |
+                          (static_cast<uint64_t>(d.interleave_mode & 3) << 4) | (d.near_lossless != 0 ? 8u : 0u) |
                           (fast_decode_eligible(d) || pixel_group_lanes(d, 1) != 0 ? 4u : 0u) |
                           (d.bits_per_sample > 8 ? 2u : 0u) | (wave_decode_eligible(d) ? 1u : 0u);
     if (!interval_decode_candidate(d))
@@ -522,7 +524,7 @@ uint64_t decode_launch_key(const ScanDesc& d) noexcept
     // interval-parallel decode also needs equal height and restart interval (both < 2^16 here, as is the width)
     return (uint64_t{1} << 63) | (static_cast<uint64_t>(d.restart_interval) << 47) | (static_cast<uint64_t>(d.height) << 31) |
            (static_cast<uint64_t>(d.width & 0xFFFF) << 15) | (static_cast<uint64_t>(d.components & 7) << 12) |
-           (static_cast<uint64_t>(d.interleave_mode & 3) << 10) | (base & 7u);
+           (static_cast<uint64_t>(d.interleave_mode & 3) << 10) | (base & 15u);
 }
 
 namespace {

@@ -30,8 +30,10 @@
 // MM = v[126:127] = M << k (v127 = the mapped error).  s[92:93]: lanes whose N = RESET (or run mode); s[96:97]: lanes whose
 // code the loop does not take; s[98:99]: EXEC of the caller.
 //
-// Hazards kept by hand (the assembler does not pad inline assembly): a VALU that reads a lane mask written by a VALU comes at
-// least two instructions behind it (v_cmp -> v_cndmask); LDS results are awaited by count (LDS operations complete in order).
+// Hazards kept by hand (the assembler does not pad inline assembly): a VALU that reads an SGPR or a lane mask written by a VALU
+// comes at least two wait states behind it (v_cmp -> v_cndmask, v_readlane -> v_cmp), a lane select of v_readlane four behind
+// its write (tests/test_inline_asm_hazards_cpu.py audits both in the compiled kernels); LDS results are awaited by count (LDS
+// operations complete in order).
 
 #define JLS_SDWA(s0, s1) " dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:" s0 " src1_sel:" s1 "\n"
 
@@ -395,6 +397,7 @@
     "s_nop 3\n"                                                            /* (a lane select written by the scalar unit) */     \
     "v_readlane_b32 s81, v89, s80\n"                                                                                              \
     "s_min_u32 %[cnt], %[cnt], s81\n"                                                                                             \
+    "s_nop 0\n"                                                            /* (an SGPR written by the vector unit: 2 states) */ \
     "v_cmp_ne_u32 vcc, s81, v89\n"                                                                                                \
     "s_and_b64 s[82:83], s[82:83], vcc\n"                                                                                         \
     "s_cbranch_scc1 L_budget" SFX "%=\n"                                                                                          \
