@@ -25,10 +25,12 @@ SOURCES = [
     "device/launch_pixels_u16.hip",
     "device/launch_group_encode_u8.hip",
     "device/launch_group_encode_u16.hip",
+    "device/seek_launch.hip",
     "host/stream_reader.cpp",
     "host/scan_engine.cpp",
     "host/encoder_api.cpp",
     "host/decoder_api.cpp",
+    "host/decoder_index.cpp",
     "host/misc_api.cpp",
     "host/batch_api.cpp",
     "host/multi_device.cpp",

@@ -250,9 +250,12 @@ class CharLSLibrary:
         return Header(fi.width, fi.height, fi.bits_per_sample, fi.component_count, near.value, ilv.value, ct.value,
                       (pc.maximum_sample_value, pc.threshold1, pc.threshold2, pc.threshold3, pc.reset_value))
 
-    def decode(self, data, stride=0, destination_size=None, out=None):
+    def decode(self, data, stride=0, destination_size=None, out=None, index=None):
         """Decode a .jls byte string. Returns (Header, uint8 ndarray of the raw destination bytes).
-        out: a preallocated uint8 ndarray to decode into (cli/benchmark.cpp:40-55: allocated outside the loop)."""
+        out: a preallocated uint8 ndarray to decode into (cli/benchmark.cpp:40-55: allocated outside the loop).
+        index: a seek-point index of this stream (decode_with_index; product library only): decode through it."""
+        if index is not None:
+            return self.decode_indexed(data, index, stride)
         L = self.lib
         dec = L.charls_jpegls_decoder_create()
         if not dec:
@@ -272,6 +275,99 @@ class CharLSLibrary:
                         "decode_to_buffer")
             del keep
             return hdr, out
+        finally:
+            L.charls_jpegls_decoder_destroy(dec)
+
+    # -- seek-point index (charls_amd_jpegls_decoder_*index*, decode_rows; product library only) ------------------------
+    def _index_fns(self):
+        L, vp, sz, u32, i32 = self.lib, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int32
+        if getattr(self, "_index_ready", False):
+            return L
+        for name, args in (("charls_amd_jpegls_decoder_get_index_size", [vp, u32, C.POINTER(sz)]),
+                           ("charls_amd_jpegls_decoder_decode_to_buffer_and_index", [vp, vp, sz, u32, u32, vp, sz, C.POINTER(sz)]),
+                           ("charls_amd_jpegls_decoder_set_index", [vp, vp, sz]),
+                           ("charls_amd_jpegls_decoder_decode_rows", [vp, u32, u32, vp, sz, u32])):
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = i32
+        self._index_ready = True
+        return L
+
+    def _open(self, data):
+        L = self.lib
+        dec = L.charls_jpegls_decoder_create()
+        if not dec:
+            raise MemoryError
+        ptr, n, keep = self._buf(data)
+        try:
+            self._check(L.charls_jpegls_decoder_set_source_buffer(dec, ptr, n), "set_source_buffer")
+            self._check(L.charls_jpegls_decoder_read_header(dec), "read_header")
+        except Exception:
+            L.charls_jpegls_decoder_destroy(dec)
+            raise
+        return dec, keep
+
+    def set_index(self, dec, index):
+        L = self._index_fns()
+        iptr, ilen, ikeep = self._buf(index)
+        self._check(L.charls_amd_jpegls_decoder_set_index(dec, iptr, ilen), "set_index")
+        del ikeep
+
+    def decode_with_index(self, data, lines_per_seek_point=64, stride=0):
+        """decode_to_buffer that also builds the seek-point index: (Header, raw destination bytes, index bytes)."""
+        L = self._index_fns()
+        dec, keep = self._open(data)
+        try:
+            hdr = self._header(dec)
+            sz = C.c_size_t()
+            self._check(L.charls_jpegls_decoder_get_destination_size(dec, stride, C.byref(sz)), "get_dest_size")
+            out = np.zeros(sz.value, dtype=np.uint8)
+            isz = C.c_size_t()
+            self._check(L.charls_amd_jpegls_decoder_get_index_size(dec, lines_per_seek_point, C.byref(isz)), "get_index_size")
+            index = np.zeros(max(isz.value, 1), dtype=np.uint8)
+            written = C.c_size_t()
+            self._check(L.charls_amd_jpegls_decoder_decode_to_buffer_and_index(
+                dec, out.ctypes.data, out.nbytes, stride, lines_per_seek_point, index.ctypes.data, isz.value, C.byref(written)),
+                "decode_to_buffer_and_index")
+            del keep
+            return hdr, out, index[:written.value].tobytes()
+        finally:
+            L.charls_jpegls_decoder_destroy(dec)
+
+    def decode_indexed(self, data, index, stride=0):
+        """decode_to_buffer through a seek-point index (set_index first): (Header, raw destination bytes)."""
+        L = self._index_fns()
+        dec, keep = self._open(data)
+        try:
+            hdr = self._header(dec)
+            self.set_index(dec, index)
+            sz = C.c_size_t()
+            self._check(L.charls_jpegls_decoder_get_destination_size(dec, stride, C.byref(sz)), "get_dest_size")
+            out = np.zeros(sz.value, dtype=np.uint8)
+            self._check(L.charls_jpegls_decoder_decode_to_buffer(dec, out.ctypes.data, out.nbytes, stride), "decode_to_buffer")
+            del keep
+            return hdr, out
+        finally:
+            L.charls_jpegls_decoder_destroy(dec)
+
+    def decode_rows(self, data, first_row, row_count, index=None, stride=0):
+        """Rows [first_row, first_row + row_count) in decode_to_buffer's layout for a frame of row_count rows (planar
+        frames: one band per component).  With `index`, from the seek point at or before first_row."""
+        L = self._index_fns()
+        dec, keep = self._open(data)
+        try:
+            hdr = self._header(dec)
+            if index is not None:
+                self.set_index(dec, index)
+            bps = (hdr.bits_per_sample + 7) // 8
+            row = hdr.width * bps * (hdr.component_count if hdr.interleave_mode != 0 else 1)
+            st = stride or row
+            scans = hdr.component_count if hdr.interleave_mode == 0 else 1
+            out = np.zeros(st * row_count * scans - (st - row), dtype=np.uint8)
+            self._check(L.charls_amd_jpegls_decoder_decode_rows(dec, first_row, row_count, out.ctypes.data, out.nbytes, stride),
+                        "decode_rows")
+            del keep
+            return out
         finally:
             L.charls_jpegls_decoder_destroy(dec)
 
@@ -324,3 +420,14 @@ def engine_counters(lib: CharLSLibrary | None = None) -> dict:
     names = ("calls", "launches", "merged_calls", "largest_launch", "pipeline_fallback_scans", "split_launches", "idle_pool_bytes",
              "deferred_free_bytes", "idle_releases", "exact_retry_scans")
     return dict(zip(names[:n], (int(v) for v in out[:n])))
+
+
+def index_counters(lib: CharLSLibrary | None = None) -> dict:
+    """charls_amd_index_counters: scans decoded from seek points, wavefronts launched from them, scans whose index did not
+    hold and that were decoded from the top."""
+    L = (lib or load_product()).lib
+    L.charls_amd_index_counters.argtypes = [C.POINTER(C.c_uint64), C.c_int32]
+    L.charls_amd_index_counters.restype = C.c_int32
+    out = (C.c_uint64 * 3)()
+    n = L.charls_amd_index_counters(out, 3)
+    return dict(zip(("scans_from_points", "intervals", "fallback_scans")[:n], (int(v) for v in out[:n])))

@@ -20,6 +20,7 @@
 #include "scan_group_decode.hip"
 #include "group_launch.h"
 #include "restart_intervals.hip"
+#include "seek_decode.h"
 
 namespace jls::dev {
 
@@ -509,6 +510,11 @@ void launch_wave_decode(int nc, const ScanDesc* d_descs, ScanResult* d_results, 
     }
 }
 } // namespace
+
+bool seek_decode_eligible(const ScanDesc& d) noexcept
+{
+    return d.restart_interval == 0 && wave_decode_eligible(d);
+}
 
 uint64_t decode_launch_key(const ScanDesc& d) noexcept
 {

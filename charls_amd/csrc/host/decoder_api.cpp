@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "scan_engine.h"
+#include "seek_index.h"
 #include "stream_reader.h"
 
 using namespace jls;
@@ -26,6 +27,7 @@ struct charls_jpegls_decoder
 
     void check_header_read() const { check_operation(state >= State::header_read); }
     void check_completed() const { check_operation(state == State::completed); }
+    void check_operation_header_read() const { check_operation(state == State::header_read); }
 
     size_t minimum_stride() const noexcept // reference :238-244
     {
@@ -180,10 +182,11 @@ struct charls_jpegls_decoder
         size_t dst_left = destination_size_bytes;
         const uint8_t* base = reader.position();
         bool uploaded = false;
-        if (decode_planes_together(dst, dst_left, stride_arg, base, uploaded))
+        if (index_mode == IndexMode::none && decode_planes_together(dst, dst_left, stride_arg, base, uploaded))
             return;
 
-        for (size_t component = 0;;)
+        ScanSpec first{};
+        for (size_t component = 0, scan_no = 0;; ++scan_no)
         {
             // reference :211-236
             const size_t min_stride = minimum_stride();
@@ -216,7 +219,13 @@ struct charls_jpegls_decoder
                 engine.upload_stream(base, reader.remaining(), frame_hint(f.width, f.height, f.bits_per_sample));
                 uploaded = true;
             }
-            const size_t used = engine.decode_scan(spec, static_cast<size_t>(reader.position() - base), dst, stride);
+            if (scan_no == 0)
+                first = spec;
+            const size_t offset = static_cast<size_t>(reader.position() - base);
+            const size_t used = index_mode == IndexMode::none
+                                    ? engine.decode_scan(spec, offset, dst, stride)
+                                    : decode_scan_indexed(engine, spec, first, offset, reader.position(), reader.remaining(), dst, stride,
+                                                          scan_no, index_mode, index, !reader.height_from_dnl());
             reader.advance(used);
 
             component += reader.scan_component_count();
@@ -236,6 +245,10 @@ struct charls_jpegls_decoder
     State state{State::initial};
     StreamReader reader;
     ScanEngine engine;
+    // the seek-point index (seek_index.h): the one set_index gave, or the one a decode_to_buffer_and_index collects
+    IndexMode index_mode{IndexMode::none};
+    bool has_index{};
+    SeekIndex index;
 };
 
 #define JLS_THUNK_BEGIN try {
@@ -356,8 +369,91 @@ charls_jpegls_errc charls_jpegls_decoder_decode_to_buffer(charls_jpegls_decoder*
                                                           uint32_t stride)
 {
     JLS_THUNK_BEGIN
-    check_pointer(d)->decode(destination, size, stride);
+    check_pointer(d);
+    d->index_mode = d->has_index ? IndexMode::use : IndexMode::none;
+    struct Reset
+    {
+        charls_jpegls_decoder* d;
+        ~Reset() { d->index_mode = IndexMode::none; }
+    } reset{d};
+    d->decode(destination, size, stride);
     JLS_THUNK_END
+}
+
+charls_jpegls_errc charls_amd_jpegls_decoder_get_index_size(const charls_jpegls_decoder* d, uint32_t lines_per_seek_point,
+                                                            size_t* bytes)
+{
+    JLS_THUNK_BEGIN
+    check_pointer(d)->check_operation_header_read();
+    const size_t value = index_size_bound(d->reader, lines_per_seek_point);
+    *check_pointer(bytes) = value;
+    JLS_THUNK_END
+}
+
+charls_jpegls_errc charls_amd_jpegls_decoder_decode_to_buffer_and_index(charls_jpegls_decoder* d, void* destination, size_t size,
+                                                                        uint32_t stride, uint32_t lines_per_seek_point, void* index,
+                                                                        size_t index_capacity, size_t* index_bytes)
+{
+    JLS_THUNK_BEGIN
+    check_pointer(d);
+    check_pointer(index_bytes);
+    check_buffer(index, index_capacity);
+    check_operation(d->state == D::State::header_read);
+    // (checked before decoding: no index is written when anything fails)
+    check_argument(index_capacity >= index_size_bound(d->reader, lines_per_seek_point), CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+    const StreamReader header = d->reader; // (the header as read: write_index describes the frame by its first scan)
+    SeekIndex built;
+    built.lines = lines_per_seek_point;
+    std::swap(built, d->index);
+    d->index_mode = IndexMode::build;
+    try
+    {
+        d->decode(destination, size, stride);
+    }
+    catch (...)
+    {
+        d->index_mode = IndexMode::none;
+        std::swap(built, d->index);
+        throw;
+    }
+    d->index_mode = IndexMode::none;
+    std::swap(built, d->index);
+    *index_bytes = write_index(header, built, static_cast<uint8_t*>(index), index_capacity);
+    JLS_THUNK_END
+}
+
+charls_jpegls_errc charls_amd_jpegls_decoder_set_index(charls_jpegls_decoder* d, const void* index, size_t bytes)
+{
+    JLS_THUNK_BEGIN
+    check_pointer(d)->check_operation_header_read();
+    check_buffer(index, bytes);
+    SeekIndex parsed = parse_index(d->reader, static_cast<const uint8_t*>(index), bytes);
+    d->index = std::move(parsed);
+    d->has_index = true;
+    JLS_THUNK_END
+}
+
+charls_jpegls_errc charls_amd_jpegls_decoder_decode_rows(charls_jpegls_decoder* d, uint32_t first_row, uint32_t row_count,
+                                                         void* destination, size_t size, uint32_t stride)
+{
+    JLS_THUNK_BEGIN
+    check_pointer(d);
+    check_buffer(destination, size);
+    check_operation(d->state == D::State::header_read);
+    const CallScope call(d->engine);
+    decode_rows(d->reader, d->engine, d->has_index ? &d->index : nullptr, first_row, row_count, static_cast<uint8_t*>(destination),
+                size, stride);
+    JLS_THUNK_END
+}
+
+int32_t charls_amd_index_counters(uint64_t* out, int32_t capacity)
+{
+    uint64_t v[3];
+    index_counters(v);
+    int32_t n = 0;
+    for (; out != nullptr && n < capacity && n < 3; ++n)
+        out[n] = v[n];
+    return n;
 }
 
 charls_jpegls_errc charls_jpegls_decoder_at_comment(charls_jpegls_decoder* d, charls_at_comment_handler handler,

@@ -33,6 +33,7 @@ struct EngineResources
     hipStream_t stream{};
     int device{-1};
     dev::DeviceBuffer pixels, bits, scratch, desc, result;
+    dev::DeviceBuffer seek_points, seek_work; // the seek-point index's calls (decoder_index.cpp)
     dev::PinnedBuffer staging;
     EngineResources() = default;
     EngineResources(const EngineResources&) = delete;
@@ -41,7 +42,8 @@ struct EngineResources
     size_t pooled_bytes{}; // what the pool counted for this set when it came back
     size_t device_bytes() const noexcept
     {
-        return pixels.capacity() + bits.capacity() + scratch.capacity() + desc.capacity() + result.capacity();
+        return pixels.capacity() + bits.capacity() + scratch.capacity() + desc.capacity() + result.capacity() +
+               seek_points.capacity() + seek_work.capacity();
     }
 };
 
@@ -98,6 +100,23 @@ public:
     // results[c] is the result of scan c; fetch_decoded_plane copies its rows out.
     void decode_planes(const ScanSpec& spec, const size_t* stream_offsets, uint32_t count, ScanResult* results);
     void fetch_decoded_plane(const ScanSpec& spec, uint32_t index, uint8_t* destination, size_t stride);
+
+    // ---- seek-point index (bodies in decoder_index.cpp).  These launch on their own: they do not take part in the
+    // coalescer's merged launches.  `lines` is K, the lines between seek points; a scan has points_per_scan(height, K)
+    // points of seek::point_bytes each, back to back (seek_decode.h).
+    bool seek_eligible(const ScanSpec& spec) const; // the exact wave decoder takes the scan, and it has no restart intervals
+    // decode_scan on the kernel that also writes the scan's seek points (to `points`, host memory).
+    size_t decode_scan_emit(const ScanSpec& spec, size_t stream_offset, uint8_t* destination, size_t stride, uint32_t lines,
+                            uint8_t* points);
+    // decode_scan as intervals that start from the seek points, one wavefront each.  True, with the rows written and the
+    // bytes consumed in `used`, when every interval decoded and ended in exactly the state of the next point; false, with
+    // nothing written, otherwise.
+    bool decode_scan_resumed(const ScanSpec& spec, size_t stream_offset, uint8_t* destination, size_t stride, uint32_t lines,
+                             const uint8_t* points, size_t& used);
+    // Rows [first_row, first_row + rows) of a scan, from the seek point at or before first_row (points != nullptr) or from
+    // the top; the decode stops after the band.  Raises what the exact decoder meets on the way.
+    void decode_scan_band(const ScanSpec& spec, size_t stream_offset, uint8_t* destination, size_t stride, uint32_t first_row,
+                          uint32_t rows, uint32_t lines, const uint8_t* points);
 
     // A coding call is coming on this handle: announced to the coalescer, so that calls of other threads that are about to
     // launch a batch this one can join wait for it (coalescer.h).  Before the coding call (the decoder was given its source,

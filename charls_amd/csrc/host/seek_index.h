@@ -1,0 +1,80 @@
+// seek_index.h -- the seek-point index of a JPEG-LS stream (include/charls_amd.h, "seek-point index").
+//
+// A portable sidecar: little-endian, no pointers, the same bytes on any device.
+//   header (72 bytes)
+//      0  magic "JLSSEEK\0"            8  uint32 version (1)         12  uint32 K, lines between seek points
+//     16  uint32 width                20  uint32 height              24  int32 bits per sample
+//     28  int32 components            32  int32 interleave mode      36  int32 NEAR
+//     40  int32 T1, T2, T3, RESET (the validated preset parameters of the first scan)
+//     56  int32 color transformation  60  uint32 scans               64  uint32 bytes per seek point   68  uint32 0
+//   per scan (24 bytes): uint64 length of its entropy-coded segment, uint64 hash of that segment (segment_hash),
+//                        uint32 seek points (0, or points_per_scan(height, K)), uint32 0
+//   the seek points, scan after scan (seek_decode.h has their layout)
+// An index is untrusted input: parse_index range-checks every field before anything can reach a kernel.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "stream_reader.h"
+
+namespace jls {
+
+class ScanEngine;
+struct ScanSpec;
+
+constexpr uint32_t kIndexVersion = 1;
+constexpr size_t kIndexHeaderBytes = 72;
+constexpr size_t kIndexScanBytes = 24;
+
+struct IndexScan
+{
+    uint64_t segment_bytes{};
+    uint64_t hash{};
+    uint32_t points{};
+    std::vector<uint8_t> data; // points x point_bytes
+};
+
+struct SeekIndex
+{
+    uint32_t lines{};
+    std::vector<IndexScan> scans;
+};
+
+// 64 bits of the bytes [p, p + n): 8 bytes per step (DESIGN 4.4b has its cost).
+uint64_t segment_hash(const uint8_t* p, size_t n) noexcept;
+
+// What the decoder of part 1 does with the seek-point index during one decode_to_buffer.
+enum class IndexMode
+{
+    none,  // the ordinary decode
+    build, // decode on the kernel that writes seek points; the index is collected in `index`
+    use,   // decode through `index`
+};
+
+// Bytes of the index of the stream whose header `reader` has read, for K = lines: an upper bound (scans that turn out to
+// have other coding parameters than the first get no seek points).  Raises invalid_argument for lines = 0.
+size_t index_size_bound(const StreamReader& reader, uint32_t lines);
+// The index in `data`, checked against the header `reader` has read: format, frame, every field's range.  Raises
+// invalid_argument for anything out of order.  Needs no GPU.
+SeekIndex parse_index(const StreamReader& reader, const uint8_t* data, size_t bytes);
+// The index collected during a decode (IndexMode::build) -> `out`; returns its size.
+size_t write_index(const StreamReader& reader, const SeekIndex& index, uint8_t* out, size_t capacity);
+
+// One scan of decode_to_buffer under an index mode: returns the source bytes consumed, raises what decode_scan raises.
+// `scan_no` counts the scans of the frame; `segment` points at the scan's first entropy-coded byte (host), with
+// `segment_left` bytes of source behind it.
+// `first`: the first scan's parameters (the index's); `seek_allowed`: false when the frame's height came from DNL.
+size_t decode_scan_indexed(ScanEngine& engine, const ScanSpec& spec, const ScanSpec& first, size_t stream_offset, const uint8_t* segment,
+                           size_t segment_left, uint8_t* destination, size_t stride, size_t scan_no, IndexMode mode, SeekIndex& index,
+                           bool seek_allowed);
+
+// charls_amd_jpegls_decoder_decode_rows: `reader` is behind the first SOS and is not moved.
+void decode_rows(const StreamReader& reader, ScanEngine& engine, const SeekIndex* index, uint32_t first_row, uint32_t row_count,
+                 uint8_t* destination, size_t destination_size, size_t stride);
+
+// charls_amd_index_counters: scans decoded from seek points, intervals launched, scans decoded from the top after their
+// index did not hold.
+void index_counters(uint64_t out[3]) noexcept;
+
+} // namespace jls

@@ -66,6 +66,7 @@ public:
         return out;
     }
     bool end_of_image() const noexcept { return state_ == State::after_eoi; }
+    bool height_from_dnl() const noexcept { return dnl_expected_; } // the frame's height came from a DNL segment
     size_t component_count() const noexcept { return components_.size(); }
     uint32_t scan_component_count() const noexcept { return scan_components_; }
     int32_t scan_interleave_mode() const noexcept { return scan_ilv_; }

@@ -415,6 +415,52 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_devices_release_work_areas(charls_a
 CHARLS_AMD_API charls_jpegls_errc charls_amd_jpegls_encoder_set_restart_interval(charls_jpegls_encoder* encoder,
                                                                                  uint32_t lines);
 
+/* Extension: the seek-point index of the decoder of part 1.  A JPEG-LS decoder's state at a line boundary is
+ * small and complete (the contexts, RUNindex, the previous line, the bit position); saved every K lines during one decode,
+ * it lets a later decode of the same stream start one wavefront per K lines -- interval-parallel decoding of streams that
+ * have no restart markers -- and decode a band of rows without the rows above the seek point before it.
+ * The index is a portable sidecar (little-endian, no pointers; layout: charls_amd/csrc/host/seek_index.h): a header that
+ * names K and the frame (width, height, bits, components, interleave mode, NEAR, T1..T3, RESET, color transformation),
+ * then per scan the length and a 64-bit hash of its entropy-coded segment and its seek points.  Scans the exact decoder
+ * does not take (lines beyond its LDS, RESET = 256 m), scans with restart intervals (already parallel) and frames whose
+ * height comes from DNL get no seek points and decode the ordinary way.
+ *
+ * get_index_size: after read_header; an upper bound of the index's bytes for K = lines_per_seek_point (>= 1).
+ * decode_to_buffer_and_index: decode_to_buffer (same pixels, errc and state transition) that also writes the index to
+ *   `index` and its size to *index_bytes; slower than a plain decode (one wavefront per scan, as the exact decoder).  An
+ *   index_capacity below get_index_size is invalid_argument_size, checked before anything is decoded; nothing is written
+ *   to `index` when the decode fails.  Indexed calls launch on their own: they are not merged with other threads' calls.
+ * set_index: after read_header; copies the index after checking its format, the frame it names and the range of every
+ *   field of every seek point (a forged or truncated index can make a decode slower, never make a kernel read or write
+ *   out of bounds).  invalid_argument, and nothing kept, on any mismatch.  Needs no GPU.  decode_to_buffer then decodes
+ *   every scan that has seek points as intervals that start from them, and accepts the result only when every interval
+ *   ends in exactly the state the next seek point claims (by induction from the true initial state the output is then
+ *   exact, whatever the index holds); a scan whose segment hash differs or whose chain does not hold is decoded from the
+ *   top (charls_amd_index_counters [2]).
+ * decode_rows: after read_header, and leaves the handle there (one handle can decode many bands).  Rows
+ *   [first_row, first_row + row_count) in decode_to_buffer's layout for a frame of row_count rows (planar frames: one band
+ *   per component, back to back; stride 0 = packed).  With an index the decode of each scan starts at the seek point at or
+ *   before first_row; a band cannot be checked by chaining, so the index is TRUSTED once its segment hash matches the
+ *   stream (invalid_argument otherwise): set only an index that was built from this stream.  Without an index the decode
+ *   starts at the top on the exact decoder (~1.3 MPix/s for one stream: a band far down a large frame then takes longer
+ *   than decode_to_buffer, which runs on the faster group decoder).  Either way it stops after the band: damage inside or above the band gives the exact decoder's errc,
+ *   damage below it is not looked at.  Scans without seek points (restart intervals, the cases above) are decoded whole on
+ *   the ordinary path and the band is copied out. */
+CHARLS_AMD_API charls_jpegls_errc charls_amd_jpegls_decoder_get_index_size(const charls_jpegls_decoder* decoder,
+                                                                           uint32_t lines_per_seek_point, size_t* bytes);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_jpegls_decoder_decode_to_buffer_and_index(
+    charls_jpegls_decoder* decoder, void* destination_buffer, size_t destination_size_bytes, uint32_t stride,
+    uint32_t lines_per_seek_point, void* index, size_t index_capacity, size_t* index_bytes);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_jpegls_decoder_set_index(charls_jpegls_decoder* decoder, const void* index,
+                                                                      size_t index_size_bytes);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_jpegls_decoder_decode_rows(charls_jpegls_decoder* decoder, uint32_t first_row,
+                                                                        uint32_t row_count, void* destination_buffer,
+                                                                        size_t destination_size_bytes, uint32_t stride);
+/* What the seek-point index did since the library was loaded (process-wide): out[0] scans decoded from seek points (full
+ * decodes and bands), out[1] wavefronts launched from the index (intervals and bands), out[2] scans whose index did not
+ * hold (hash or chain check) and that were decoded from the top.  Returns the number of values written (3 at most). */
+CHARLS_AMD_API int32_t charls_amd_index_counters(uint64_t* out, int32_t capacity);
+
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */
 CHARLS_AMD_API charls_jpegls_errc charls_amd_set_encode_engine(int32_t engine);
