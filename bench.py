@@ -14,12 +14,17 @@ Correctness is checked outside the timed region: every frame must round-trip bit
 must hash to the committed golden produced by the reference (tests/golden/cases.json: cfg2_full).
 
 One JSON line is printed by rank 0 (see the driver contract): it carries `roofline` for the dominant kernel
-(HIP-event time of that kernel on its own stream, algorithmic bytes per launch) and `cpu_baseline` (the reference's
+(HIP-event time of that kernel on its own stream, algorithmic bytes per launch).  A plain run does nothing else: it sets up,
+warms up, times the steps, checks them, writes --dump-outputs if asked and prints the line.
+
+`--full` adds what takes runs of its own after the timed steps, none of it `value`: `cpu_baseline` (the reference's
 CPU codec, or the oracle port when oracle/_ref did not travel, timed on this box's host cores: one thread, and one
-handle per thread on all cores).  Extra keys outside `value`: `batch_sweep` (throughput against the number
-of frames in flight), `data_sweep` (the same engine on other data), `single_frame_ms` (one frame through the host-pointer C ABI),
-`batch_api_host_buffers` (the batch API fed from pinned host memory) and `threads_abi` (the 48-symbol ABI under a pool of host
-threads -- the harness `cpu_baseline.all_cores` uses for CharLS); all PCIe inclusive, none of them `value`.
+handle per thread on all cores) and, at N = 1 on the headline workload, the extra keys of SURVEY 8d: `batch_sweep`
+(throughput against the number of frames in flight), `data_sweep` (the same engine on other data), `near_lossless` (NEAR = 2),
+`single_frame_ms` (one frame through the host-pointer C ABI), `batch_api_host_buffers` (the batch API fed from pinned host
+memory), `threads_abi` (the 48-symbol ABI under a pool of host threads -- the harness `cpu_baseline.all_cores` uses for
+CharLS; PCIe inclusive, as the two before it) and `value_natural_image`.  `--no-cpu-baseline` / `--no-extras` leave out
+either part of `--full`.
 
 `python bench.py --workload cfg4 --gpus N` runs BASELINE configs[3] as stated instead: 256 frames of 2048x2048 split over the N
 ranks (strong scaling), bitstreams gathered to rank 0 inside the clock.
@@ -35,6 +40,7 @@ import sys
 import threading
 import time
 
+T_IMPORT = time.perf_counter()  # (the phases of a run are logged against this)
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for p in (ROOT, os.path.join(ROOT, "tests")):
     if p not in sys.path:
@@ -297,8 +303,14 @@ def main():
     ap.add_argument("--threads-abi", default="",
                     help="thread counts of the `threads_abi` extra (host threads x handles through the 48-symbol ABI); default: the "
                          "host's hardware threads and twice that")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip batch_sweep / data_sweep / single_frame_ms / batch_api_host_buffers / threads_abi")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the context of `value` in runs of their own: cpu_baseline and, at "
+                         "N = 1 on the headline workload, batch_sweep / data_sweep / near_lossless / single_frame_ms / "
+                         "batch_api_host_buffers / threads_abi / value_natural_image (minutes; never part of `value`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip batch_sweep / data_sweep / near_lossless / single_frame_ms / batch_api_host_buffers / "
+                         "threads_abi / value_natural_image")
     ap.add_argument("--selftest-exchange", action="store_true", help="launcher + exchange on fabricated streams (no codec)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one handed its caller (rank 0's .jls streams and decoded frames: "
@@ -373,6 +385,7 @@ def main():
     streams = torch.empty((frames_n, pitch), dtype=torch.uint8, device=dev)
     out = torch.empty_like(frames)
     torch.cuda.synchronize()
+    t_setup = time.perf_counter()
 
     enc_ms, dec_ms, enc_kernel_ms, dec_kernel_ms = [], [], [], []
 
@@ -424,6 +437,7 @@ def main():
 
     barrier()
     t_start = time.perf_counter()
+    t_warm = t_start - t_setup
     for _ in range(args.steps):
         enc, errcs = step(True)
     barrier()
@@ -446,6 +460,9 @@ def main():
         assert bit_exact, "frame 0 differs from the reference's .jls (golden hash)"
     if rank == 0 and args.dump_outputs:  # before the extras: they reuse `frames`, `streams` and `out`
         dump_outputs(args.dump_outputs, torch, enc, errcs, out)
+    if rank == 0:
+        log(f"set-up {t_setup - T_IMPORT:.1f} s after import, warm-up {t_warm:.1f} s, timed steps {elapsed:.1f} s, "
+            f"checks{' and dump' if args.dump_outputs else ''} {time.perf_counter() - t_start - elapsed:.1f} s")
 
     if rank == 0:
         pixels = WIDTH * HEIGHT
@@ -541,9 +558,9 @@ def main():
         }
         # (context for `value` and the CPU baseline: at N = 1 only -- the other ranks of a multi-GPU run would sit in the process
         # group for minutes while rank 0 measures them)
-        if not args.no_extras and args.restart_interval == 0 and args.workload == "cfg2" and world == 1:
+        if args.full and not args.no_extras and args.restart_interval == 0 and args.workload == "cfg2" and world == 1:
             line.update(extras(lib, batch, torch, frames, streams, out, enc, dev, mpix, pitch, args))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline()
         # ---- context, never `value`: SURVEY 8(d)'s methodology (host buffer in -> host buffer out) and the whole host CPU
         if "batch_api_host_buffers" in line:
