@@ -61,6 +61,21 @@ def _bind(lib):
     l.charls_amd_decode_batch_devices.argtypes = [C.c_uint32, C.POINTER(DeviceShard), C.c_size_t, C.POINTER(C.c_uint64),
                                                   C.c_size_t, C.c_uint32, C.POINTER(CodecParams), C.POINTER(C.c_int32)]
     l.charls_amd_decode_batch_devices.restype = C.c_int32
+    u64p, i32p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+    l.charls_amd_index_size_bound.argtypes = [C.POINTER(CodecParams), C.c_uint32, C.POINTER(C.c_size_t)]
+    l.charls_amd_index_size_bound.restype = C.c_int32
+    l.charls_amd_decode_batch_device_and_index.argtypes = [C.c_uint32, C.c_void_p, C.c_size_t, u64p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                           C.c_uint32, C.c_void_p, C.c_size_t, u64p, C.POINTER(CodecParams), i32p,
+                                                           C.c_void_p]
+    l.charls_amd_decode_batch_device_and_index.restype = C.c_int32
+    l.charls_amd_decode_batch_device_indexed.argtypes = [C.c_uint32, C.c_void_p, C.c_size_t, u64p, C.c_void_p, C.c_size_t, u64p,
+                                                         C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(CodecParams), i32p, C.c_void_p]
+    l.charls_amd_decode_batch_device_indexed.restype = C.c_int32
+    l.charls_amd_decode_rows_batch_device.argtypes = [C.c_uint32, C.c_void_p, C.c_size_t, u64p, C.c_void_p, C.c_size_t, u64p, u32p, u32p,
+                                                      C.c_void_p, C.c_size_t, C.c_uint32, i32p, C.c_void_p]
+    l.charls_amd_decode_rows_batch_device.restype = C.c_int32
+    l.charls_amd_index_counters.argtypes = [u64p, C.c_int32]
+    l.charls_amd_index_counters.restype = C.c_int32
     l._batch_bound = True
     return l
 
@@ -138,6 +153,135 @@ def decode_batch(streams, sizes, out, *, lib=None):
     if rc != 0:
         raise capi.JpegLSError(rc, "charls_amd_decode_batch_device")
     return p, errcs, last_timings(lib)
+
+
+# ---- the seek-point index in the batch API (charls_amd.h part 2c): indexes are host bytes, everything else stays in HBM ----
+
+def index_size_bound(width, height, bits_per_sample=8, component_count=1, interleave_mode=0, near_lossless=0,
+                     lines_per_seek_point=64, *, color_transformation=0, preset=(0, 0, 0, 0, 0), restart_interval=0, lib=None) -> int:
+    """charls_amd_index_size_bound: what get_index_size gives for a stream with these parameters.  Needs no GPU."""
+    l = _bind(lib or capi.load_product())
+    p = CodecParams(capi.FrameInfo(width, height, bits_per_sample, component_count), near_lossless, interleave_mode,
+                    color_transformation, capi.PcParameters(*preset), 0, restart_interval)
+    out = C.c_size_t(0)
+    rc = l.charls_amd_index_size_bound(C.byref(p), lines_per_seek_point, C.byref(out))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_index_size_bound")
+    return int(out.value)
+
+
+def seek_launches(lib=None) -> int:
+    """charls_amd_index_counters [3]: launches of the seek kernels so far (a batch call is one per group of scans)."""
+    l = _bind(lib or capi.load_product())
+    out = (C.c_uint64 * 4)()
+    n = l.charls_amd_index_counters(out, 4)
+    assert n == 4
+    return int(out[3])
+
+
+def _pack_indexes(indexes, count):
+    """[bytes or None] -> (host uint8 array (count, pitch), pitch, uint64 sizes); None / b"" = no index."""
+    assert len(indexes) == count
+    pitch = max([len(x) for x in indexes if x] + [16])
+    packed = np.zeros((count, pitch), dtype=np.uint8)
+    sizes = np.zeros(count, dtype=np.uint64)
+    for f, x in enumerate(indexes):
+        if x:
+            packed[f, :len(x)] = np.frombuffer(x, dtype=np.uint8)
+            sizes[f] = len(x)
+    return packed, pitch, sizes
+
+
+def _index_pitch_for(out, lines, lib):
+    """The largest index of a frame that fills out[f]: (H, W), planar (C, H, W) or interleaved (H, W, C), 8 or 16 bit."""
+    bits = 16 if out.element_size() == 2 else 8
+    shape = tuple(out.shape[1:])
+    if len(shape) not in (2, 3):
+        raise ValueError("index_pitch is needed: the frames' geometry cannot be read from the shape of `out`")
+    if len(shape) == 2:
+        cases = [(shape[1], shape[0], 1, 0)]
+    else:
+        cases = [(shape[2], shape[1], shape[0], 0)] + ([(shape[1], shape[0], shape[2], 2)] if shape[2] <= 4 else [])
+    return max(index_size_bound(w, h, bits, c, ilv, 0, lines, lib=lib) for w, h, c, ilv in cases)
+
+
+def decode_batch_and_index(streams, sizes, out, lines_per_seek_point=64, *, index_pitch=None, stride=0, frame_pitch=None, lib=None):
+    """charls_amd_decode_batch_device_and_index: decode_batch that also builds every frame's seek-point index.
+    index_pitch: bytes kept per index (at least index_size_bound of every frame; by default that of a frame that fills
+    out[f]).  Returns (params, errcs, [index bytes]); the index of a frame that failed is b""."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    if index_pitch is None:
+        index_pitch = _index_pitch_for(out, lines_per_seek_point, lib)
+    assert streams.is_cuda and streams.is_contiguous() and out.is_cuda
+    count = streams.shape[0]
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    errcs = np.zeros(count, dtype=np.int32)
+    index_sizes = np.zeros(count, dtype=np.uint64)
+    indexes = np.zeros((count, int(index_pitch)), dtype=np.uint8)
+    p = CodecParams()
+    if frame_pitch is None:
+        frame_pitch = out[0].numel() * out.element_size()
+    stream = torch.cuda.current_stream(streams.device).cuda_stream
+    rc = l.charls_amd_decode_batch_device_and_index(count, streams.data_ptr(), streams.shape[1], sizes.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                    out.data_ptr(), frame_pitch, stride, lines_per_seek_point, indexes.ctypes.data,
+                                                    int(index_pitch), index_sizes.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(p),
+                                                    errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_decode_batch_device_and_index")
+    return p, errcs, [indexes[f, :int(index_sizes[f])].tobytes() for f in range(count)]
+
+
+def decode_batch_indexed(streams, sizes, indexes, out, *, stride=0, frame_pitch=None, lib=None):
+    """charls_amd_decode_batch_device_indexed: decode_batch through seek-point indexes (a list of bytes; None or b"" = that
+    frame decodes the ordinary way).  Returns (params, errcs)."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert streams.is_cuda and streams.is_contiguous() and out.is_cuda
+    count = streams.shape[0]
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    errcs = np.zeros(count, dtype=np.int32)
+    packed, pitch, index_sizes = _pack_indexes(indexes, count)
+    p = CodecParams()
+    if frame_pitch is None:
+        frame_pitch = out[0].numel() * out.element_size()
+    stream = torch.cuda.current_stream(streams.device).cuda_stream
+    rc = l.charls_amd_decode_batch_device_indexed(count, streams.data_ptr(), streams.shape[1], sizes.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                  packed.ctypes.data, pitch, index_sizes.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                  out.data_ptr(), frame_pitch, stride, C.byref(p),
+                                                  errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_decode_batch_device_indexed")
+    return p, errcs
+
+
+def decode_rows_batch(streams, sizes, indexes, first_rows, row_counts, bands, *, stride=0, band_pitch=None, lib=None):
+    """charls_amd_decode_rows_batch_device: rows [first_rows[f], first_rows[f] + row_counts[f]) of frame f into bands[f]
+    (decode_rows' layout), through the frame's index where indexes[f] is one, from the top otherwise.  Returns errcs."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert streams.is_cuda and streams.is_contiguous() and bands.is_cuda
+    count = streams.shape[0]
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    first_rows = np.ascontiguousarray(first_rows, dtype=np.uint32)
+    row_counts = np.ascontiguousarray(row_counts, dtype=np.uint32)
+    assert len(first_rows) == count and len(row_counts) == count
+    errcs = np.zeros(count, dtype=np.int32)
+    packed, pitch, index_sizes = _pack_indexes(indexes, count)
+    if band_pitch is None:
+        band_pitch = bands[0].numel() * bands.element_size()
+    stream = torch.cuda.current_stream(streams.device).cuda_stream
+    rc = l.charls_amd_decode_rows_batch_device(count, streams.data_ptr(), streams.shape[1], sizes.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               packed.ctypes.data, pitch, index_sizes.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               first_rows.ctypes.data_as(C.POINTER(C.c_uint32)), row_counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               bands.data_ptr(), band_pitch, stride, errcs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_decode_rows_batch_device")
+    return errcs
 
 
 def set_workspace_limit(nbytes: int, lib=None):

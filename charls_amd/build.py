@@ -26,6 +26,7 @@ SOURCES = [
     "device/launch_group_encode_u8.hip",
     "device/launch_group_encode_u16.hip",
     "device/seek_launch.hip",
+    "device/segment_hash.hip",
     "host/stream_reader.cpp",
     "host/scan_engine.cpp",
     "host/encoder_api.cpp",
@@ -33,6 +34,7 @@ SOURCES = [
     "host/decoder_index.cpp",
     "host/misc_api.cpp",
     "host/batch_api.cpp",
+    "host/batch_index.cpp",
     "host/multi_device.cpp",
 ]
 

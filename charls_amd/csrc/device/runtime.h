@@ -147,6 +147,10 @@ uint64_t workspace_limit() noexcept;          // as set (0: the default rule)
 void release_shared_work_areas() noexcept;    // the shared sets of the host-pointer ABI's merged launches, all devices (a launch that runs finishes first)
 size_t shared_work_area_bytes() noexcept;     // what they hold
 DeviceBuffer& plane_arena(); // the calling thread's private stream buffers of the planar batch encoder (a work area)
+// The calling thread's buffers of the seek-point index's batch calls (host/batch_index.cpp): seek points, work items, descs,
+// results, hash jobs (work areas: counted by work_area_bytes, freed by release_work_areas).
+constexpr int kSeekArenas = 6;
+DeviceBuffer& seek_arena(int which);
 void* try_ensure(DeviceBuffer& buffer, size_t bytes) noexcept; // ensure() that reports failure (nullptr; the buffer is released) instead of raising
 void release_work_areas() noexcept;
 size_t work_area_bytes() noexcept;

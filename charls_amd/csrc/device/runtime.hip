@@ -577,12 +577,14 @@ struct PipelineLanes
 constexpr int kIntervalArenas = 8;
 struct WorkAreas
 {
-    DeviceBuffer pipeline, plane, interval[kIntervalArenas];
+    DeviceBuffer pipeline, plane, interval[kIntervalArenas], seek[kSeekArenas];
     PipelineLanes lanes;
     size_t bytes() const noexcept
     {
         size_t total = pipeline.capacity() + plane.capacity();
         for (const DeviceBuffer& b : interval)
+            total += b.capacity();
+        for (const DeviceBuffer& b : seek)
             total += b.capacity();
         return total;
     }
@@ -591,6 +593,8 @@ struct WorkAreas
         pipeline.release();
         plane.release();
         for (DeviceBuffer& b : interval)
+            b.release();
+        for (DeviceBuffer& b : seek)
             b.release();
     }
 };
@@ -1471,6 +1475,11 @@ void launch_encode(const ScanDesc& proto, ScanDesc* d_descs, ScanResult* d_resul
 DeviceBuffer& plane_arena()
 {
     return areas().plane;
+}
+
+DeviceBuffer& seek_arena(int which)
+{
+    return areas().seek[which];
 }
 
 size_t work_area_budget() noexcept

@@ -77,6 +77,13 @@ struct SeekWork
     uint64_t to_point;
 };
 
+// One job of segment_hash_kernel (segment_hash.hip): the bytes [offset, offset + bytes) of a batch's stream slots.
+struct HashJob
+{
+    uint64_t offset; // from the first slot; no alignment
+    uint64_t bytes;  // 0 included
+};
+
 } // namespace jls::seek
 
 #ifdef __HIPCC__
@@ -90,6 +97,8 @@ void launch_seek_emit(const ScanDesc& proto, const ScanDesc* d_descs, ScanResult
 // One interval (or band) per wavefront; all work items share proto's geometry and coding mode.
 void launch_seek_resume(const ScanDesc& proto, const ScanDesc* d_descs, const seek::SeekWork* d_work, ScanResult* d_results,
                         uint32_t count, const uint8_t* d_points, hipStream_t stream);
+// d_out[j] = jls::segment_hash of job j's bytes (seek_index.h), one wavefront per job.
+void launch_segment_hash(const uint8_t* d_slots, const seek::HashJob* d_jobs, uint64_t* d_out, uint32_t count, hipStream_t stream);
 
 } // namespace jls::dev
 #endif

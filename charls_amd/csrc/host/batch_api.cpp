@@ -17,29 +17,12 @@
 #include "preset.h"
 #include "stream_reader.h"
 #include "stream_writer.h"
+#include "window_fetch.h"
 
 using namespace jls;
 using dev::hip_check;
 
 namespace {
-// One window of every listed stream -> a contiguous staging buffer (then ONE device-to-host copy instead of one small,
-// synchronously staged copy per frame: 4096 of those were 60 ms per round of the batch decoder).
-struct WindowSpec
-{
-    uint64_t offset; // from the first slot
-    uint32_t bytes;
-    uint32_t pad;
-};
-__global__ void gather_windows(const uint8_t* __restrict__ slots, const WindowSpec* __restrict__ specs, uint8_t* __restrict__ out,
-                               uint32_t window)
-{
-    const WindowSpec w = specs[blockIdx.x];
-    const uint8_t* src = slots + w.offset;
-    uint8_t* dst = out + (size_t)blockIdx.x * window;
-    for (uint32_t b = threadIdx.x; b < w.bytes; b += blockDim.x)
-        dst[b] = src[b];
-}
-
 struct EventTimer
 {
     hipEvent_t a{}, b{};

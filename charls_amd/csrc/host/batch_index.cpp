@@ -1,0 +1,1231 @@
+// batch_index.cpp -- the seek-point index in the batch API (charls_amd.h part 2c): building the indexes of many
+// device-resident streams in one call, decoding many frames through their indexes, decoding many row bands.
+//
+// Per frame the contract is part 1's (decoder_index.cpp), and the index is parsed, checked and written by the same
+// functions (seek_index.h).  What is new is the shape of the work: all scans of a call that share the seek kernels'
+// specialisation (sample width, components per pixel) are ONE launch over one ScanDesc array, one work list and one
+// seek-point buffer, the resumed wavefronts store straight into the caller's frames or bands, and the segment hashes
+// are computed where the streams are (device/segment_hash.hip).
+//   build:  rounds per scan ordinal (scan c + 1 starts where scan c ended): one emit launch per group and round.
+//   use:    the index names every segment's length, so the host walks to every SOS first; then one hash launch and
+//           one resume launch per group for all scans of all frames.
+//   bands:  as use, with the work items of decode_rows.
+// A frame whose index does not hold, or that gets no seek points, is decoded in the same call by the ordinary launches
+// (charls_amd_decode_batch_device on every run of such frames).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <functional>
+#include <vector>
+
+#include "../device/runtime.h"
+#include "../device/seek_decode.h"
+#include "common.h"
+#include "preset.h"
+#include "seek_index.h"
+#include "stream_reader.h"
+#include "window_fetch.h"
+
+using namespace jls;
+using dev::hip_check;
+
+namespace {
+
+constexpr size_t kWindow = 2048;
+
+enum : int
+{ // dev::seek_arena
+    kArenaPoints = 0,
+    kArenaWork = 1,
+    kArenaDescs = 2,
+    kArenaResults = 3,
+    kArenaHash = 4,
+    kArenaFrame = 5, // a whole frame of the bands' ordinary path
+};
+
+// GPU time of the seek launches and of the hash launches of the running call (charls_amd_last_timings [0] and [1]).
+thread_local double t_seek_ms = 0, t_hash_ms = 0;
+class GpuClock
+{
+public:
+    GpuClock(hipStream_t stream, double& total) : stream_(stream), total_(total)
+    {
+        hip_check(hipEventCreate(&a_));
+        if (hipEventCreate(&b_) != hipSuccess)
+        {
+            (void)hipEventDestroy(a_);
+            raise(CHARLS_AMD_ERRC_DEVICE_FAILURE);
+        }
+        (void)hipEventRecord(a_, stream_);
+    }
+    GpuClock(const GpuClock&) = delete;
+    GpuClock& operator=(const GpuClock&) = delete;
+    void stop() { (void)hipEventRecord(b_, stream_); } // before the synchronisation that follows the launch
+    ~GpuClock()
+    { // (behind that synchronisation)
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, a_, b_) == hipSuccess)
+            total_ += ms;
+        else
+            (void)hipGetLastError();
+        (void)hipEventDestroy(a_);
+        (void)hipEventDestroy(b_);
+    }
+
+private:
+    hipEvent_t a_{}, b_{};
+    hipStream_t stream_;
+    double& total_;
+};
+void timings_begin() noexcept
+{
+    t_seek_ms = t_hash_ms = 0;
+}
+void timings_end() noexcept
+{
+    dev::Timings& t = dev::last_timings();
+    t.values[0] = t_seek_ms;
+    t.values[1] = t_hash_ms;
+    t.count = 2;
+}
+
+struct Frame
+{
+    StreamReader reader;
+    std::vector<uint8_t> window; // host copy of [window_base, window_base + window.size())
+    size_t window_base{};
+    size_t cursor{};       // absolute offset of the next unparsed byte
+    size_t plane_offset{}; // destination offset of the next scan
+    uint32_t decoded_components{};
+    charls_jpegls_errc errc{};
+    bool done{};
+};
+
+// The streams of a call and the host's windows into them: charls_amd_decode_batch_device's way of parsing.
+class Streams
+{
+public:
+    Streams(uint32_t count, const void* d_streams, size_t pitch, const uint64_t* sizes_arg, hipStream_t s)
+        : slots(static_cast<const uint8_t*>(d_streams)), stream_pitch(pitch), sizes(sizes_arg), stream(s), fr(count)
+    {
+        if (pitch == 0)
+            raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+        for (uint32_t i = 0; i < count; ++i)
+            if (sizes[i] > pitch)
+                raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+    }
+
+    void fetch(Frame& x, uint32_t i, size_t base, size_t bytes)
+    {
+        const size_t avail = base < sizes[i] ? static_cast<size_t>(sizes[i]) - base : 0;
+        const size_t n = std::min(bytes, avail);
+        x.window.resize(n);
+        x.window_base = base;
+        if (n)
+            hip_check(hipMemcpyAsync(x.window.data(), slots + i * stream_pitch + base, n, hipMemcpyDeviceToHost, stream));
+    }
+    // one gather on the device, one copy (bases[k] is the offset of frame which[k]'s window)
+    void fetch_many(std::vector<Frame>& set, const std::vector<uint32_t>& which, const std::vector<size_t>& bases)
+    {
+        const size_t n = which.size();
+        if (n == 0)
+            return;
+        auto* specs = static_cast<WindowSpec*>(h_specs_.ensure(sizeof(WindowSpec) * n));
+        for (size_t k = 0; k < n; ++k)
+        {
+            const uint32_t i = which[k];
+            const size_t avail = bases[k] < sizes[i] ? static_cast<size_t>(sizes[i]) - bases[k] : 0;
+            specs[k] = WindowSpec{static_cast<uint64_t>(i) * stream_pitch + bases[k], static_cast<uint32_t>(std::min(kWindow, avail)), 0};
+        }
+        d_specs_.ensure(sizeof(WindowSpec) * n);
+        d_windows_.ensure(kWindow * n);
+        auto* staged = static_cast<uint8_t*>(h_windows_.ensure(kWindow * n));
+        hip_check(hipMemcpyAsync(d_specs_.as<WindowSpec>(), specs, sizeof(WindowSpec) * n, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(gather_windows, dim3(static_cast<uint32_t>(n)), dim3(256), 0, stream, slots, d_specs_.as<const WindowSpec>(),
+                           d_windows_.as<uint8_t>(), static_cast<uint32_t>(kWindow));
+        hip_check(hipGetLastError());
+        hip_check(hipMemcpyAsync(staged, d_windows_.as<uint8_t>(), kWindow * n, hipMemcpyDeviceToHost, stream));
+        hip_check(hipStreamSynchronize(stream));
+        for (size_t k = 0; k < n; ++k)
+        {
+            Frame& x = set[which[k]];
+            x.window.assign(staged + k * kWindow, staged + k * kWindow + specs[k].bytes);
+            x.window_base = bases[k];
+        }
+    }
+    // A parse that runs off the end of the window while the stream has more bytes is retried with a larger window.
+    template <typename Body>
+    void parse(std::vector<Frame>& set, uint32_t i, Body&& body)
+    {
+        Frame& x = set[i];
+        size_t want = kWindow;
+        const StreamReader snapshot = x.reader;
+        for (;;)
+        {
+            try
+            {
+                body(x);
+                x.errc = CHARLS_JPEGLS_ERRC_SUCCESS;
+                return;
+            }
+            catch (const error& e)
+            {
+                const bool truncated = x.window_base + x.window.size() < sizes[i];
+                if (!truncated || (e.code != CHARLS_JPEGLS_ERRC_NEED_MORE_DATA && e.code != CHARLS_JPEGLS_ERRC_INVALID_MARKER_SEGMENT_SIZE &&
+                                   e.code != CHARLS_JPEGLS_ERRC_DEFINE_NUMBER_OF_LINES_MARKER_NOT_FOUND))
+                {
+                    x.errc = e.code;
+                    x.done = true;
+                    return;
+                }
+            }
+            want *= 8;
+            fetch(x, i, x.window_base, want);
+            hip_check(hipStreamSynchronize(stream));
+            x.reader = snapshot;
+        }
+    }
+    void read_headers()
+    {
+        const uint32_t n = static_cast<uint32_t>(fr.size());
+        std::vector<uint32_t> all(n);
+        for (uint32_t i = 0; i < n; ++i)
+            all[i] = i;
+        fetch_many(fr, all, std::vector<size_t>(n, 0));
+        for (uint32_t i = 0; i < n; ++i)
+            parse(fr, i, [&](Frame& x) {
+                x.reader.set_source(x.window.data(), x.window.size());
+                x.reader.read_header();
+                if (x.reader.end_of_image())
+                    raise(CHARLS_JPEGLS_ERRC_INVALID_OPERATION); // abbreviated table stream: nothing to decode
+                x.cursor = x.window_base + static_cast<size_t>(x.reader.position() - x.window.data());
+            });
+    }
+    // The frames `which` stand at `bases` (behind a scan): what follows is parsed on fresh windows, the next SOS, or the end
+    // of the image where last[k].
+    void parse_behind_scans(std::vector<Frame>& set, const std::vector<uint32_t>& which, const std::vector<size_t>& bases,
+                            const std::vector<uint8_t>& last)
+    {
+        fetch_many(set, which, bases);
+        for (size_t k = 0; k < which.size(); ++k)
+        {
+            const bool end = last[k] != 0;
+            parse(set, which[k], [&](Frame& y) {
+                y.reader.continue_on_window(y.window.data(), y.window.size());
+                if (end)
+                    y.reader.read_end_of_image();
+                else
+                    y.reader.read_next_start_of_scan();
+                y.cursor = y.window_base + static_cast<size_t>(y.reader.position() - y.window.data());
+            });
+        }
+    }
+
+    const uint8_t* slots;
+    size_t stream_pitch;
+    const uint64_t* sizes;
+    hipStream_t stream;
+    std::vector<Frame> fr;
+
+private:
+    dev::DeviceBuffer d_specs_, d_windows_;
+    dev::PinnedBuffer h_specs_, h_windows_;
+};
+
+ScanDesc desc_from(const ScanSpec& s) noexcept
+{
+    ScanDesc d{};
+    d.width = s.width;
+    d.height = s.height;
+    d.components = s.components;
+    d.interleave_mode = s.interleave_mode;
+    d.bits_per_sample = s.bits_per_sample;
+    d.near_lossless = s.near_lossless;
+    d.color_transformation = s.color_transformation;
+    d.t1 = s.pc.threshold1;
+    d.t2 = s.pc.threshold2;
+    d.t3 = s.pc.threshold3;
+    d.reset = static_cast<uint8_t>(s.pc.reset_value);
+    d.restart_interval = s.restart_interval;
+    return d;
+}
+
+size_t planes_of(const ScanSpec& s) noexcept
+{
+    return s.interleave_mode == 0 ? 1u : static_cast<size_t>(s.components);
+}
+size_t row_bytes_of(const ScanSpec& s) noexcept
+{
+    return planes_of(s) * s.width * bytes_per_sample(s.bits_per_sample);
+}
+
+// The scan whose header x's reader has read, decoding to `frames + i * frame_pitch` with the checks
+// charls_amd_decode_batch_device makes (stride, extent).  No line scratch.
+ScanDesc frame_scan_desc(const Streams& s, uint32_t i, const Frame& x, uint8_t* frames, size_t frame_pitch, uint32_t stride_arg)
+{
+    const ScanSpec spec = scan_spec_of(x.reader);
+    const size_t row = row_bytes_of(spec);
+    size_t stride = stride_arg;
+    if (stride == 0)
+        stride = row;
+    else if (stride < row)
+        raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_STRIDE);
+    const size_t need = stride * spec.height - (stride - row); // (a scan of ILV_NONE is one component)
+    if (frame_pitch < x.plane_offset + need)
+        raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+    ScanDesc d = desc_from(spec);
+    d.pixels = frames + i * frame_pitch + x.plane_offset;
+    d.pixel_stride = stride;
+    d.stream = const_cast<uint8_t*>(s.slots) + i * s.stream_pitch + x.cursor;
+    d.stream_capacity = s.sizes[i] - x.cursor;
+    d.line_scratch = nullptr; // (the seek kernels keep their lines in LDS)
+    return d;
+}
+
+// The seek kernels store samples with the sample's width: 16-bit rows must start at even addresses (part 1's device rows
+// are packed; here the base, the pitch and the stride are the caller's).
+bool rows_aligned(const ScanDesc& d) noexcept
+{
+    return d.bits_per_sample <= 8 || ((reinterpret_cast<uintptr_t>(d.pixels) | d.pixel_stride) & 1u) == 0;
+}
+
+// Scans with the same key share a launch of the seek kernels; the dynamic LDS of a launch is its largest scan's.
+uint32_t seek_group(const ScanDesc& d) noexcept
+{
+    return (d.bits_per_sample > 8 ? 8u : 0u) | static_cast<uint32_t>(d.interleave_mode == 2 ? d.components : 1);
+}
+size_t seek_line_bytes(const ScanDesc& d) noexcept
+{
+    return (d.interleave_mode == 0 ? 1u : static_cast<size_t>(d.components)) * (static_cast<size_t>(d.width) + 2) * (d.bits_per_sample > 8 ? 2 : 1);
+}
+
+// What one pass may keep in the device seek-point buffer: half of what the thread's work areas may still grow to.
+size_t points_budget() noexcept
+{
+    return std::max<size_t>(dev::work_area_budget() / 2, size_t{64} << 20);
+}
+
+std::vector<uint32_t> sorted_by_group(const std::vector<ScanDesc>& descs)
+{
+    std::vector<uint32_t> order(descs.size());
+    for (uint32_t k = 0; k < order.size(); ++k)
+        order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return seek_group(descs[a]) < seek_group(descs[b]); });
+    return order;
+}
+
+// decode_scans_wave_emit over descs[k], all k: results[k], and the seek points of scan k (point_totals[k] bytes) to
+// points_out[k].  One launch per group and pass.
+void run_emit(const std::vector<ScanDesc>& descs, const std::vector<size_t>& point_totals, const std::vector<uint8_t*>& points_out,
+              uint32_t lines, std::vector<ScanResult>& results, hipStream_t stream)
+{
+    const uint32_t n = static_cast<uint32_t>(descs.size());
+    results.assign(n, ScanResult{});
+    const std::vector<uint32_t> order = sorted_by_group(descs);
+    const size_t budget = points_budget();
+    for (uint32_t first = 0; first < n;)
+    {
+        uint32_t last = first;
+        size_t stride = 16;
+        uint32_t proto = order[first];
+        while (last < n && seek_group(descs[order[last]]) == seek_group(descs[order[first]]))
+        {
+            stride = std::max(stride, (point_totals[order[last]] + 15) & ~size_t{15});
+            if (seek_line_bytes(descs[order[last]]) > seek_line_bytes(descs[proto]))
+                proto = order[last];
+            ++last;
+        }
+        const uint32_t per_pass = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>(last - first, budget / stride)));
+        for (uint32_t at = first; at < last; at += per_pass)
+        {
+            const uint32_t count = std::min(per_pass, last - at);
+            std::vector<ScanDesc> pass(count);
+            for (uint32_t k = 0; k < count; ++k)
+                pass[k] = descs[order[at + k]];
+            auto* d_points = static_cast<uint8_t*>(dev::seek_arena(kArenaPoints).ensure(stride * count));
+            auto* d_descs = static_cast<ScanDesc*>(dev::seek_arena(kArenaDescs).ensure(dev::with_headroom(sizeof(ScanDesc) * count)));
+            auto* d_results = static_cast<ScanResult*>(dev::seek_arena(kArenaResults).ensure(dev::with_headroom(sizeof(ScanResult) * count)));
+            std::vector<ScanResult> got(count);
+            hip_check(hipMemcpyAsync(d_descs, pass.data(), sizeof(ScanDesc) * count, hipMemcpyHostToDevice, stream));
+            {
+                GpuClock clock(stream, t_seek_ms);
+                dev::launch_seek_emit(descs[proto], d_descs, d_results, count, d_points, stride, lines, stream);
+                clock.stop();
+                add_index_counters(0, 0, 0, 1);
+                hip_check(hipMemcpyAsync(got.data(), d_results, sizeof(ScanResult) * count, hipMemcpyDeviceToHost, stream));
+                hip_check(hipStreamSynchronize(stream));
+            }
+            for (uint32_t k = 0; k < count; ++k)
+            {
+                const uint32_t scan = order[at + k];
+                results[scan] = got[k];
+                if (got[k].errc == kOk && point_totals[scan] != 0)
+                    hip_check(hipMemcpyAsync(points_out[scan], d_points + stride * k, point_totals[scan], hipMemcpyDeviceToHost, stream));
+            }
+            hip_check(hipStreamSynchronize(stream));
+        }
+        first = last;
+    }
+}
+
+// One scan of a resume launch: its seek points (host) and its work items, whose point offsets count from the scan's first
+// point.
+struct ResumeScan
+{
+    ScanDesc desc;
+    const uint8_t* points{};
+    size_t point_total{};
+    std::vector<seek::SeekWork> work;
+    std::vector<ScanResult> results; // beside work
+};
+
+// decode_scans_wave_resume over every work item of every scan.  One launch per group and pass.
+void run_resume(std::vector<ResumeScan>& scans, hipStream_t stream)
+{
+    const uint32_t n = static_cast<uint32_t>(scans.size());
+    std::vector<ScanDesc> descs(n);
+    for (uint32_t k = 0; k < n; ++k)
+        descs[k] = scans[k].desc;
+    const std::vector<uint32_t> order = sorted_by_group(descs);
+    const size_t budget = points_budget();
+    for (uint32_t first = 0; first < n;)
+    {
+        // a pass: scans of one group whose points fit the budget (one scan always does)
+        uint32_t last = first;
+        size_t total = 0, items = 0;
+        uint32_t proto = order[first];
+        while (last < n && seek_group(descs[order[last]]) == seek_group(descs[order[first]]))
+        {
+            const size_t bytes = (scans[order[last]].point_total + 15) & ~size_t{15};
+            if (last > first && total + bytes > budget)
+                break;
+            total += bytes;
+            items += scans[order[last]].work.size();
+            if (seek_line_bytes(descs[order[last]]) > seek_line_bytes(descs[proto]))
+                proto = order[last];
+            ++last;
+        }
+        const uint32_t count = last - first;
+        auto* d_points = static_cast<uint8_t*>(dev::seek_arena(kArenaPoints).ensure(std::max<size_t>(total, 16)));
+        auto* d_descs = static_cast<ScanDesc*>(dev::seek_arena(kArenaDescs).ensure(dev::with_headroom(sizeof(ScanDesc) * count)));
+        auto* d_work = static_cast<seek::SeekWork*>(dev::seek_arena(kArenaWork).ensure(dev::with_headroom(sizeof(seek::SeekWork) * items)));
+        auto* d_results = static_cast<ScanResult*>(dev::seek_arena(kArenaResults).ensure(dev::with_headroom(sizeof(ScanResult) * items)));
+        std::vector<ScanDesc> pass(count);
+        std::vector<seek::SeekWork> work;
+        work.reserve(items);
+        size_t at = 0;
+        for (uint32_t k = 0; k < count; ++k)
+        {
+            const ResumeScan& s = scans[order[first + k]];
+            pass[k] = s.desc;
+            if (s.point_total != 0)
+                hip_check(hipMemcpyAsync(d_points + at, s.points, s.point_total, hipMemcpyHostToDevice, stream));
+            for (seek::SeekWork w : s.work)
+            {
+                w.scan = k;
+                w.from_point += at;
+                w.to_point += at;
+                work.push_back(w);
+            }
+            at += (s.point_total + 15) & ~size_t{15};
+        }
+        std::vector<ScanResult> got(items);
+        if (items != 0)
+        {
+            hip_check(hipMemcpyAsync(d_descs, pass.data(), sizeof(ScanDesc) * count, hipMemcpyHostToDevice, stream));
+            hip_check(hipMemcpyAsync(d_work, work.data(), sizeof(seek::SeekWork) * items, hipMemcpyHostToDevice, stream));
+            GpuClock clock(stream, t_seek_ms);
+            dev::launch_seek_resume(descs[proto], d_descs, d_work, d_results, static_cast<uint32_t>(items), d_points, stream);
+            clock.stop();
+            add_index_counters(0, items, 0, 1);
+            hip_check(hipMemcpyAsync(got.data(), d_results, sizeof(ScanResult) * items, hipMemcpyDeviceToHost, stream));
+            hip_check(hipStreamSynchronize(stream));
+        }
+        hip_check(hipStreamSynchronize(stream));
+        size_t item = 0;
+        for (uint32_t k = 0; k < count; ++k)
+        {
+            ResumeScan& s = scans[order[first + k]];
+            s.results.assign(got.begin() + item, got.begin() + item + s.work.size());
+            item += s.work.size();
+        }
+        first = last;
+    }
+}
+
+// segment_hash of the bytes [offset, offset + bytes) of the slots, job by job, on the device.
+std::vector<uint64_t> device_hashes(const Streams& s, const std::vector<seek::HashJob>& jobs)
+{
+    const size_t n = jobs.size();
+    std::vector<uint64_t> out(n);
+    if (n == 0)
+        return out;
+    const size_t jobs_bytes = (sizeof(seek::HashJob) * n + 15) & ~size_t{15};
+    auto* area = static_cast<uint8_t*>(dev::seek_arena(kArenaHash).ensure(dev::with_headroom(jobs_bytes + sizeof(uint64_t) * n)));
+    hip_check(hipMemcpyAsync(area, jobs.data(), sizeof(seek::HashJob) * n, hipMemcpyHostToDevice, s.stream));
+    GpuClock clock(s.stream, t_hash_ms);
+    dev::launch_segment_hash(s.slots, reinterpret_cast<const seek::HashJob*>(area), reinterpret_cast<uint64_t*>(area + jobs_bytes),
+                             static_cast<uint32_t>(n), s.stream);
+    clock.stop();
+    hip_check(hipMemcpyAsync(out.data(), area + jobs_bytes, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, s.stream));
+    hip_check(hipStreamSynchronize(s.stream));
+    return out;
+}
+
+// The ordinary launches for one round of scans that get no seek points (the build call needs every scan's length, which
+// charls_amd_decode_batch_device does not report): as its run_scans.
+void run_ordinary(std::vector<ScanDesc>& descs, std::vector<ScanResult>& results, hipStream_t stream)
+{
+    const uint32_t n = static_cast<uint32_t>(descs.size());
+    results.assign(n, ScanResult{});
+    if (n == 0)
+        return;
+    dev::DeviceBuffer d_descs, d_results, d_scratch;
+    size_t scratch_total = 0;
+    std::vector<size_t> scratch_at(n);
+    for (uint32_t k = 0; k < n; ++k)
+    {
+        scratch_at[k] = scratch_total;
+        scratch_total += dev::line_scratch_samples(descs[k].width, descs[k].interleave_mode, descs[k].components) * sizeof(uint16_t);
+        scratch_total = (scratch_total + 255) & ~size_t{255};
+    }
+    auto* scratch = static_cast<uint8_t*>(d_scratch.ensure(scratch_total));
+    std::vector<uint32_t> order(n);
+    for (uint32_t k = 0; k < n; ++k)
+    {
+        order[k] = k;
+        descs[k].line_scratch = reinterpret_cast<uint16_t*>(scratch + scratch_at[k]);
+    }
+    std::stable_sort(order.begin(), order.end(),
+                     [&](uint32_t a, uint32_t b) { return dev::decode_launch_key(descs[a]) < dev::decode_launch_key(descs[b]); });
+    std::vector<ScanDesc> sorted(n);
+    for (uint32_t k = 0; k < n; ++k)
+        sorted[k] = descs[order[k]];
+    d_descs.ensure(sizeof(ScanDesc) * n);
+    d_results.ensure(sizeof(ScanResult) * n);
+    hip_check(hipMemcpyAsync(d_descs.as<ScanDesc>(), sorted.data(), sizeof(ScanDesc) * n, hipMemcpyHostToDevice, stream));
+    for (uint32_t first = 0; first < n;)
+    {
+        uint32_t last = first + 1;
+        while (last < n && dev::decode_launch_key(sorted[last]) == dev::decode_launch_key(sorted[first]))
+            ++last;
+        dev::launch_decode(sorted[first], d_descs.as<ScanDesc>() + first, d_results.as<ScanResult>() + first, last - first, stream);
+        first = last;
+    }
+    std::vector<ScanResult> got(n);
+    hip_check(hipMemcpyAsync(got.data(), d_results.as<ScanResult>(), sizeof(ScanResult) * n, hipMemcpyDeviceToHost, stream));
+    hip_check(hipStreamSynchronize(stream));
+    for (uint32_t k = 0; k < n; ++k)
+        results[order[k]] = got[k];
+}
+
+charls_amd_codec_params params_of(const StreamReader& r)
+{
+    return charls_amd_codec_params{r.frame_info(), r.parameters().near_lossless, r.scan_interleave_mode(), r.parameters().transformation,
+                                   r.preset_coding_parameters(), 0, r.parameters().restart_interval};
+}
+
+// Every run of frames marked in `ordinary` through charls_amd_decode_batch_device; params_out as that call documents it
+// (params_from: the lowest frame whose parameters it holds so far).
+charls_jpegls_errc decode_ordinary(const Streams& s, const std::vector<uint8_t>& ordinary, uint8_t* frames, size_t frame_pitch,
+                                   uint32_t stride, charls_amd_codec_params* params_out, uint32_t& params_from, charls_jpegls_errc* errcs)
+{
+    const uint32_t n = static_cast<uint32_t>(ordinary.size());
+    for (uint32_t i = 0; i < n;)
+    {
+        if (!ordinary[i])
+        {
+            ++i;
+            continue;
+        }
+        uint32_t last = i + 1;
+        while (last < n && ordinary[last])
+            ++last;
+        charls_amd_codec_params got{};
+        const charls_jpegls_errc rc =
+            charls_amd_decode_batch_device(last - i, s.slots + i * s.stream_pitch, s.stream_pitch, s.sizes + i, frames + i * frame_pitch,
+                                           frame_pitch, stride, &got, errcs + i, s.stream);
+        if (rc != CHARLS_JPEGLS_ERRC_SUCCESS)
+            return rc;
+        if (params_out && got.frame_info.width != 0 && i < params_from)
+        { // (the run's lowest frame that got as far as a scan is not known: no frame before the run's first can be it)
+            *params_out = got;
+            params_from = i;
+        }
+        i = last;
+    }
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+
+// set_index for every frame that has one: parsed[i] (empty scans: none), errors to the frame.
+void parse_indexes(Streams& s, const void* indexes, size_t index_pitch, const uint64_t* index_sizes, std::vector<SeekIndex>& parsed)
+{
+    const uint32_t n = static_cast<uint32_t>(s.fr.size());
+    parsed.assign(n, SeekIndex{});
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        Frame& x = s.fr[i];
+        if (x.done || index_sizes[i] == 0)
+            continue;
+        try
+        {
+            check_argument(index_sizes[i] <= index_pitch, CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+            parsed[i] = parse_index(x.reader, static_cast<const uint8_t*>(indexes) + i * index_pitch, static_cast<size_t>(index_sizes[i]));
+        }
+        catch (const error& e)
+        {
+            x.errc = e.code;
+            x.done = true;
+        }
+    }
+}
+
+// The walk over a frame's scans that an index allows: scan c starts at starts[c], its descriptor is descs[c].
+struct Walk
+{
+    uint32_t frame{};
+    std::vector<ScanDesc> descs;
+    std::vector<ScanSpec> specs;
+    std::vector<size_t> starts;
+    bool ok{true};
+    bool beyond{}; // a scan with seek points whose length, as the index has it, runs past the stream's end
+};
+
+} // namespace
+
+extern "C" charls_jpegls_errc charls_amd_index_size_bound(const charls_amd_codec_params* params, uint32_t lines_per_seek_point, size_t* bytes)
+try
+{
+    check_pointer(params);
+    check_pointer(bytes);
+    check_argument(lines_per_seek_point > 0);
+    const charls_frame_info& f = params->frame_info;
+    check_argument(f.width >= 1 && f.height >= 1 && f.bits_per_sample >= kMinBits && f.bits_per_sample <= kMaxBits && f.component_count >= 1 &&
+                   f.component_count <= kMaxComponents);
+    check_argument(params->interleave_mode >= 0 && params->interleave_mode <= 2);
+    check_argument(params->interleave_mode == 0 || f.component_count <= kMaxComponentsInScan);
+    ScanSpec first{};
+    first.width = f.width;
+    first.height = f.height;
+    first.components = params->interleave_mode == 0 ? 1 : f.component_count;
+    first.interleave_mode = params->interleave_mode;
+    first.bits_per_sample = f.bits_per_sample;
+    first.near_lossless = params->near_lossless;
+    first.color_transformation = params->color_transformation;
+    first.restart_interval = params->restart_interval;
+    if (!pc_validate(params->preset_coding_parameters, bit_max_value(f.bits_per_sample), params->near_lossless, &first.pc))
+        raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT);
+    const size_t scans = params->interleave_mode == 0 ? static_cast<size_t>(f.component_count) : 1u;
+    *bytes = index_size_bound(first, scans, false, lines_per_seek_point);
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}
+
+extern "C" charls_jpegls_errc charls_amd_decode_batch_device_and_index(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
+                                                                       const uint64_t* sizes, void* d_frames, size_t frame_pitch_bytes,
+                                                                       uint32_t stride_arg, uint32_t lines, void* indexes,
+                                                                       size_t index_pitch_bytes, uint64_t* index_sizes,
+                                                                       charls_amd_codec_params* params_out, charls_jpegls_errc* errcs,
+                                                                       void* hip_stream)
+try
+{
+    check_pointer(sizes);
+    check_pointer(errcs);
+    check_pointer(index_sizes);
+    check_argument(lines > 0);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    check_pointer(d_streams);
+    check_pointer(d_frames);
+    check_pointer(indexes);
+    dev::require_device();
+    auto stream = static_cast<hipStream_t>(hip_stream);
+    auto* frames = static_cast<uint8_t*>(d_frames);
+    Streams s(frame_count, d_streams, stream_pitch_bytes, sizes, stream);
+    timings_begin();
+    s.read_headers();
+
+    struct Build
+    {
+        StreamReader header; // as read: write_index describes the frame by its first scan
+        ScanSpec first{};
+        SeekIndex index;
+    };
+    std::vector<Build> builds(frame_count);
+    for (uint32_t i = 0; i < frame_count; ++i)
+    {
+        Frame& x = s.fr[i];
+        index_sizes[i] = 0;
+        if (x.done)
+            continue;
+        try
+        { // (checked before decoding: nothing of a frame whose index cannot be kept is decoded)
+            check_argument(index_pitch_bytes >= index_size_bound(x.reader, lines), CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+            builds[i].header = x.reader;
+            builds[i].first = scan_spec_of(x.reader);
+            builds[i].index.lines = lines;
+        }
+        catch (const error& e)
+        {
+            x.errc = e.code;
+            x.done = true;
+        }
+    }
+
+    uint32_t params_from = UINT32_MAX;
+    for (size_t scan_no = 0;; ++scan_no)
+    {
+        std::vector<uint32_t> emit_frames, plain_frames;
+        std::vector<ScanDesc> emit_descs, plain_descs;
+        std::vector<size_t> point_totals;
+        std::vector<uint8_t*> points_out;
+        for (uint32_t i = 0; i < frame_count; ++i)
+        {
+            Frame& x = s.fr[i];
+            if (x.done)
+                continue;
+            try
+            {
+                const ScanDesc d = frame_scan_desc(s, i, x, frames, frame_pitch_bytes, stride_arg);
+                if (params_out && i < params_from)
+                {
+                    *params_out = params_of(x.reader);
+                    params_from = i;
+                }
+                const ScanSpec spec = scan_spec_of(x.reader);
+                Build& b = builds[i];
+                b.index.scans.resize(scan_no + 1);
+                IndexScan& rec = b.index.scans[scan_no];
+                const bool eligible = !x.reader.height_from_dnl() && same_scan_parameters(spec, b.first) && seek_spec_eligible(spec) && rows_aligned(d);
+                rec.points = eligible ? seek::points_per_scan(spec.height, lines) : 0u;
+                rec.data.assign(static_cast<size_t>(rec.points) * seek_point_bytes(spec), 0);
+                if (rec.points != 0)
+                {
+                    emit_frames.push_back(i);
+                    emit_descs.push_back(d);
+                    point_totals.push_back(rec.data.size());
+                    points_out.push_back(rec.data.data());
+                }
+                else
+                {
+                    plain_frames.push_back(i);
+                    plain_descs.push_back(d);
+                }
+            }
+            catch (const error& e)
+            {
+                x.errc = e.code;
+                x.done = true;
+            }
+        }
+        if (emit_frames.empty() && plain_frames.empty())
+            break;
+        std::vector<ScanResult> emit_results, plain_results;
+        run_emit(emit_descs, point_totals, points_out, lines, emit_results, stream);
+        run_ordinary(plain_descs, plain_results, stream);
+
+        // every scan's length and hash; then past it, to the next SOS or the end of the image
+        std::vector<uint32_t> which;
+        std::vector<size_t> bases;
+        std::vector<uint8_t> last;
+        std::vector<seek::HashJob> jobs;
+        auto scan_done = [&](uint32_t i, const ScanResult& r) {
+            Frame& x = s.fr[i];
+            if (r.errc != kOk)
+            {
+                x.errc = static_cast<charls_jpegls_errc>(r.errc);
+                x.done = true;
+                return;
+            }
+            if (r.bytes > sizes[i] - x.cursor)
+            { // (cannot happen: a scan is decoded from the bytes of its stream; the hash kernel must not be handed more)
+                x.errc = CHARLS_JPEGLS_ERRC_INVALID_DATA;
+                x.done = true;
+                return;
+            }
+            builds[i].index.scans[scan_no].segment_bytes = r.bytes;
+            jobs.push_back(seek::HashJob{static_cast<uint64_t>(i) * stream_pitch_bytes + x.cursor, r.bytes});
+            x.cursor += r.bytes;
+            x.decoded_components += x.reader.scan_component_count();
+            const bool end = x.decoded_components == x.reader.component_count();
+            if (!end)
+                x.plane_offset += (stride_arg ? stride_arg : row_bytes_of(scan_spec_of(x.reader))) * x.reader.frame_info().height;
+            which.push_back(i);
+            bases.push_back(x.cursor);
+            last.push_back(end ? 1 : 0);
+        };
+        for (size_t k = 0; k < emit_frames.size(); ++k)
+            scan_done(emit_frames[k], emit_results[k]);
+        for (size_t k = 0; k < plain_frames.size(); ++k)
+            scan_done(plain_frames[k], plain_results[k]);
+        const std::vector<uint64_t> hashes = device_hashes(s, jobs);
+        for (size_t k = 0; k < which.size(); ++k)
+            builds[which[k]].index.scans[scan_no].hash = hashes[k];
+        s.parse_behind_scans(s.fr, which, bases, last);
+        for (size_t k = 0; k < which.size(); ++k)
+        {
+            Frame& x = s.fr[which[k]];
+            if (x.done || !last[k])
+                continue;
+            x.done = true; // the end of the image has been read: the index is the frame's
+            try
+            {
+                index_sizes[which[k]] = write_index(builds[which[k]].header, builds[which[k]].index,
+                                                    static_cast<uint8_t*>(indexes) + which[k] * index_pitch_bytes, index_pitch_bytes);
+            }
+            catch (const error& e)
+            {
+                x.errc = e.code;
+            }
+        }
+    }
+    for (uint32_t i = 0; i < frame_count; ++i)
+        errcs[i] = s.fr[i].errc;
+    timings_end();
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}
+
+namespace {
+
+// The frames of `s` that have an index with seek points for every scan: the walk over their scans (every SOS parsed on a copy
+// of the frame, `probe`).  A frame whose walk breaks off is left out (walks[k].ok = false).
+void walk_indexed_frames(Streams& s, const std::vector<SeekIndex>& parsed, std::vector<Frame>& probe, std::vector<Walk>& walks,
+                         const std::function<ScanDesc(uint32_t, const Frame&, size_t)>& scan_desc, bool want_points)
+{
+    probe = s.fr;
+    const uint32_t n = static_cast<uint32_t>(s.fr.size());
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        if (s.fr[i].done || parsed[i].scans.empty())
+            continue;
+        Walk w;
+        w.frame = i;
+        walks.push_back(std::move(w));
+    }
+    for (size_t c = 0;; ++c)
+    {
+        std::vector<uint32_t> which;
+        std::vector<size_t> bases;
+        std::vector<size_t> of_walk;
+        for (size_t k = 0; k < walks.size(); ++k)
+        {
+            Walk& w = walks[k];
+            const SeekIndex& index = parsed[w.frame];
+            if (!w.ok || c >= index.scans.size() || w.descs.size() != c)
+                continue;
+            Frame& y = probe[w.frame];
+            try
+            {
+                const ScanSpec spec = scan_spec_of(y.reader);
+                const IndexScan& rec = index.scans[c];
+                if ((want_points && rec.points == 0) || rec.segment_bytes > s.sizes[w.frame] - y.cursor)
+                {
+                    w.beyond = rec.points != 0 && rec.segment_bytes > s.sizes[w.frame] - y.cursor;
+                    w.ok = false;
+                    continue;
+                }
+                w.descs.push_back(scan_desc(w.frame, y, c));
+                w.specs.push_back(spec);
+                w.starts.push_back(y.cursor);
+                if (c + 1 < index.scans.size())
+                {
+                    y.plane_offset += w.descs.back().pixel_stride * spec.height;
+                    which.push_back(w.frame);
+                    bases.push_back(y.cursor + static_cast<size_t>(rec.segment_bytes));
+                    of_walk.push_back(k);
+                }
+            }
+            catch (const error&)
+            {
+                w.ok = false;
+            }
+        }
+        if (which.empty())
+            break;
+        s.parse_behind_scans(probe, which, bases, std::vector<uint8_t>(which.size(), 0));
+        for (size_t q = 0; q < which.size(); ++q)
+            if (probe[which[q]].done)
+                walks[of_walk[q]].ok = false;
+    }
+    for (Walk& w : walks)
+        w.ok = w.ok && w.descs.size() == parsed[w.frame].scans.size();
+}
+
+} // namespace
+
+extern "C" charls_jpegls_errc charls_amd_decode_batch_device_indexed(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
+                                                                     const uint64_t* sizes, const void* indexes, size_t index_pitch_bytes,
+                                                                     const uint64_t* index_sizes, void* d_frames, size_t frame_pitch_bytes,
+                                                                     uint32_t stride_arg, charls_amd_codec_params* params_out,
+                                                                     charls_jpegls_errc* errcs, void* hip_stream)
+try
+{
+    check_pointer(sizes);
+    check_pointer(errcs);
+    check_pointer(index_sizes);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    check_pointer(d_streams);
+    check_pointer(d_frames);
+    check_pointer(indexes);
+    dev::require_device();
+    auto stream = static_cast<hipStream_t>(hip_stream);
+    auto* frames = static_cast<uint8_t*>(d_frames);
+    Streams s(frame_count, d_streams, stream_pitch_bytes, sizes, stream);
+    timings_begin();
+    s.read_headers();
+    std::vector<SeekIndex> parsed;
+    parse_indexes(s, indexes, index_pitch_bytes, index_sizes, parsed);
+
+    // ---- the frames that can go through their index: every scan has seek points and is one the seek kernels take
+    std::vector<Frame> probe;
+    std::vector<Walk> walks;
+    walk_indexed_frames(s, parsed, probe, walks,
+                        [&](uint32_t i, const Frame& y, size_t) { return frame_scan_desc(s, i, y, frames, frame_pitch_bytes, stride_arg); }, true);
+    std::vector<uint8_t> ordinary(frame_count, 0);
+    std::vector<uint8_t> with_points(frame_count, 0); // the frame's index has seek points: decoding it from the top is a fallback
+    for (uint32_t i = 0; i < frame_count; ++i)
+    {
+        ordinary[i] = !s.fr[i].done;
+        for (const IndexScan& rec : parsed[i].scans)
+            with_points[i] = with_points[i] || rec.points != 0;
+    }
+    std::vector<seek::HashJob> jobs;
+    for (Walk& w : walks)
+    {
+        const Frame& x = s.fr[w.frame];
+        const ScanSpec first = scan_spec_of(x.reader);
+        for (size_t c = 0; w.ok && c < w.descs.size(); ++c)
+            w.ok = !x.reader.height_from_dnl() && same_scan_parameters(w.specs[c], first) && seek_spec_eligible(w.specs[c]) &&
+                   rows_aligned(w.descs[c]);
+        for (size_t c = 0; w.ok && c < w.descs.size(); ++c)
+            jobs.push_back(seek::HashJob{static_cast<uint64_t>(w.frame) * stream_pitch_bytes + w.starts[c], parsed[w.frame].scans[c].segment_bytes});
+    }
+    {
+        const std::vector<uint64_t> hashes = device_hashes(s, jobs);
+        size_t job = 0;
+        for (Walk& w : walks)
+        {
+            if (!w.ok)
+                continue;
+            for (size_t c = 0; c < w.descs.size(); ++c)
+                if (hashes[job++] != parsed[w.frame].scans[c].hash)
+                    w.ok = false;
+        }
+    }
+    std::vector<ResumeScan> scans;
+    std::vector<std::pair<uint32_t, uint32_t>> scan_of; // (walk, scan ordinal) of scans[k]
+    for (uint32_t k = 0; k < walks.size(); ++k)
+    {
+        const Walk& w = walks[k];
+        if (!w.ok)
+            continue;
+        const SeekIndex& index = parsed[w.frame];
+        for (uint32_t c = 0; c < w.descs.size(); ++c)
+        {
+            ResumeScan r;
+            r.desc = w.descs[c];
+            r.points = index.scans[c].data.data();
+            r.point_total = index.scans[c].data.size();
+            const size_t point_bytes = seek_point_bytes(w.specs[c]);
+            const uint32_t intervals = index.scans[c].points + 1;
+            for (uint32_t i = 0; i < intervals; ++i)
+            { // (ScanEngine::decode_scan_resumed's intervals)
+                seek::SeekWork item{};
+                item.first_row = i * index.lines;
+                item.end_row = static_cast<uint32_t>(std::min<uint64_t>(w.specs[c].height, (static_cast<uint64_t>(i) + 1) * index.lines));
+                item.store_from = item.first_row;
+                item.row_base = 0;
+                item.mode = i + 1 < intervals ? seek::kResumeCompare : seek::kResumeEnd;
+                item.from_point = i == 0 ? 0 : (i - 1) * point_bytes;
+                item.to_point = i + 1 < intervals ? i * point_bytes : 0;
+                r.work.push_back(item);
+            }
+            scans.push_back(std::move(r));
+            scan_of.emplace_back(k, c);
+        }
+    }
+    run_resume(scans, stream);
+    for (size_t k = 0; k < scans.size(); ++k)
+    {
+        Walk& w = walks[scan_of[k].first];
+        const std::vector<ScanResult>& got = scans[k].results;
+        for (size_t i = 0; i + 1 < got.size(); ++i)
+            if (got[i].errc != kOk || (got[i].flags & seek::kSeekChecked) == 0 || (got[i].flags & seek::kSeekMismatch) != 0)
+                w.ok = false;
+        // (the last interval ends the scan where the index says the segment ends: the next SOS was read from there)
+        if (got.back().errc != kOk || got.back().bytes != parsed[w.frame].scans[scan_of[k].second].segment_bytes)
+            w.ok = false;
+    }
+    {
+        std::vector<uint32_t> which;
+        std::vector<size_t> bases;
+        for (const Walk& w : walks)
+        {
+            if (!w.ok)
+                continue;
+            which.push_back(w.frame);
+            bases.push_back(w.starts.back() + static_cast<size_t>(parsed[w.frame].scans.back().segment_bytes));
+        }
+        s.parse_behind_scans(probe, which, bases, std::vector<uint8_t>(which.size(), 1));
+    }
+    uint32_t params_from = UINT32_MAX;
+    uint64_t from_points = 0, fallbacks = 0;
+    for (const Walk& w : walks)
+    {
+        if (!w.ok || probe[w.frame].errc != CHARLS_JPEGLS_ERRC_SUCCESS)
+            continue; // (decoded again below, which reports what part 1 reports)
+        s.fr[w.frame].errc = CHARLS_JPEGLS_ERRC_SUCCESS;
+        s.fr[w.frame].done = true;
+        ordinary[w.frame] = 0;
+        from_points += w.descs.size();
+        if (params_out && w.frame < params_from)
+        {
+            *params_out = params_of(s.fr[w.frame].reader);
+            params_from = w.frame;
+        }
+    }
+    for (uint32_t i = 0; i < frame_count; ++i)
+        fallbacks += ordinary[i] && with_points[i];
+    add_index_counters(from_points, 0, fallbacks, 0);
+    for (uint32_t i = 0; i < frame_count; ++i)
+        errcs[i] = s.fr[i].errc;
+    const charls_jpegls_errc rc = decode_ordinary(s, ordinary, frames, frame_pitch_bytes, stride_arg, params_out, params_from, errcs);
+    timings_end(); // (this call's seek and hash launches, not the ordinary launches of the frames that went that way)
+    return rc;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}
+
+extern "C" charls_jpegls_errc charls_amd_decode_rows_batch_device(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
+                                                                  const uint64_t* sizes, const void* indexes, size_t index_pitch_bytes,
+                                                                  const uint64_t* index_sizes, const uint32_t* first_rows,
+                                                                  const uint32_t* row_counts, void* d_bands, size_t band_pitch_bytes,
+                                                                  uint32_t stride_arg, charls_jpegls_errc* errcs, void* hip_stream)
+try
+{
+    check_pointer(sizes);
+    check_pointer(errcs);
+    check_pointer(index_sizes);
+    check_pointer(first_rows);
+    check_pointer(row_counts);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    check_pointer(d_streams);
+    check_pointer(d_bands);
+    dev::require_device();
+    auto stream = static_cast<hipStream_t>(hip_stream);
+    auto* bands = static_cast<uint8_t*>(d_bands);
+    Streams s(frame_count, d_streams, stream_pitch_bytes, sizes, stream);
+    timings_begin();
+    s.read_headers();
+    std::vector<SeekIndex> parsed;
+    for (uint32_t i = 0; i < frame_count; ++i)
+        if (index_sizes[i] != 0)
+            check_pointer(indexes);
+    parse_indexes(s, indexes, index_pitch_bytes, index_sizes, parsed);
+
+    // decode_rows' argument checks; the stride of every frame
+    std::vector<size_t> strides(frame_count, 0);
+    for (uint32_t i = 0; i < frame_count; ++i)
+    {
+        Frame& x = s.fr[i];
+        if (x.done)
+            continue;
+        try
+        {
+            const charls_frame_info& f = x.reader.frame_info();
+            check_argument(row_counts[i] > 0 && first_rows[i] < f.height && row_counts[i] <= f.height - first_rows[i]);
+            const ScanSpec first = scan_spec_of(x.reader);
+            const size_t row_bytes = row_bytes_of(first);
+            const size_t stride = stride_arg == 0 ? row_bytes : stride_arg;
+            check_argument(stride >= row_bytes, CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_STRIDE);
+            const size_t needed = checked_mul(checked_mul(stride, row_counts[i]), scans_of_frame(x.reader)) - (stride - row_bytes);
+            check_argument(band_pitch_bytes >= needed, CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+            strides[i] = stride;
+        }
+        catch (const error& e)
+        {
+            x.errc = e.code;
+            x.done = true;
+        }
+    }
+    auto band_desc = [&](uint32_t i, const Frame& y, size_t c) {
+        ScanDesc d = desc_from(scan_spec_of(y.reader));
+        d.pixels = bands + i * band_pitch_bytes + strides[i] * row_counts[i] * c;
+        d.pixel_stride = strides[i];
+        d.stream = const_cast<uint8_t*>(s.slots) + i * s.stream_pitch + y.cursor;
+        d.stream_capacity = s.sizes[i] - y.cursor;
+        d.line_scratch = nullptr;
+        return d;
+    };
+
+    // ---- frames on the seek kernels: every scan is reached through the index (or the frame has one scan) and is one the
+    // kernels take; the others are decoded whole on the ordinary path
+    std::vector<Frame> probe;
+    std::vector<Walk> walks;
+    walk_indexed_frames(s, parsed, probe, walks, band_desc, false);
+    std::vector<uint8_t> whole(frame_count, 0), walked(frame_count, 0);
+    for (const Walk& w : walks)
+        walked[w.frame] = 1;
+    for (uint32_t i = 0; i < frame_count; ++i)
+    {
+        const Frame& x = s.fr[i];
+        if (x.done || walked[i])
+            continue;
+        if (scans_of_frame(x.reader) == 1)
+        { // no index: one scan from the top
+            Walk w;
+            w.frame = i;
+            w.descs.push_back(band_desc(i, x, 0));
+            w.specs.push_back(scan_spec_of(x.reader));
+            w.starts.push_back(x.cursor);
+            walks.push_back(std::move(w));
+        }
+        else
+            whole[i] = 1;
+    }
+    std::vector<seek::HashJob> jobs;
+    for (Walk& w : walks)
+    {
+        const Frame& x = s.fr[w.frame];
+        const SeekIndex& index = parsed[w.frame];
+        for (size_t c = 0; w.ok && c < w.descs.size(); ++c)
+            w.ok = !x.reader.height_from_dnl() && seek_spec_eligible(w.specs[c]) && rows_aligned(w.descs[c]);
+        // (a planar frame is walked by the lengths the index names: every one of them must be the segment's, so every scan's
+        // hash is checked, not only those of scans with seek points)
+        for (size_t c = 0; w.ok && c < index.scans.size(); ++c)
+            if (index.scans[c].points != 0 || index.scans.size() > 1)
+                jobs.push_back(seek::HashJob{static_cast<uint64_t>(w.frame) * stream_pitch_bytes + w.starts[c], index.scans[c].segment_bytes});
+        if (!w.ok)
+            whole[w.frame] = 1;
+    }
+    {
+        const std::vector<uint64_t> hashes = device_hashes(s, jobs);
+        size_t job = 0;
+        for (Walk& w : walks)
+        {
+            if (!w.ok)
+                continue;
+            const SeekIndex& index = parsed[w.frame];
+            for (size_t c = 0; c < index.scans.size(); ++c)
+                if ((index.scans[c].points != 0 || index.scans.size() > 1) && hashes[job++] != index.scans[c].hash && w.ok)
+                { // a band cannot be checked by chaining: the index must belong to this very segment
+                    w.ok = false;
+                    s.fr[w.frame].errc = CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT;
+                    s.fr[w.frame].done = true;
+                }
+        }
+    }
+    // (a walk that broke off on a frame with an index: the length of a segment beyond the stream is what decode_rows
+    // refuses as invalid_argument; anything else is the whole-frame path's to report)
+    for (Walk& w : walks)
+    {
+        if (w.ok || s.fr[w.frame].done)
+            continue;
+        if (w.beyond)
+        {
+            s.fr[w.frame].errc = CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT;
+            s.fr[w.frame].done = true;
+            whole[w.frame] = 0;
+        }
+        else
+            whole[w.frame] = 1;
+    }
+
+    std::vector<ResumeScan> scans;
+    std::vector<uint32_t> walk_of;
+    uint64_t from_points = 0;
+    for (uint32_t k = 0; k < walks.size(); ++k)
+    {
+        const Walk& w = walks[k];
+        if (!w.ok || s.fr[w.frame].done)
+            continue;
+        const SeekIndex& index = parsed[w.frame];
+        const ScanSpec first = scan_spec_of(s.fr[w.frame].reader);
+        const uint32_t first_row = first_rows[w.frame], rows = row_counts[w.frame], end = first_row + rows;
+        for (uint32_t c = 0; c < w.descs.size(); ++c)
+        {
+            ResumeScan r;
+            r.desc = w.descs[c];
+            const bool use = c < index.scans.size() && index.scans[c].points != 0 && same_scan_parameters(w.specs[c], first);
+            const uint32_t lines = use ? index.lines : 0;
+            const uint32_t count = use ? index.scans[c].points : 0u;
+            if (use)
+            {
+                r.points = index.scans[c].data.data();
+                r.point_total = index.scans[c].data.size();
+                ++from_points;
+            }
+            const size_t point_bytes = seek_point_bytes(w.specs[c]);
+            // (ScanEngine::decode_scan_band's work items: every interval the band touches is a wavefront of its own)
+            const uint32_t from = count != 0 ? std::min(first_row / lines, count) : 0u;
+            const uint32_t to = count != 0 ? std::min((end - 1) / lines, count) : 0u;
+            for (uint32_t i = from; i <= to; ++i)
+            {
+                seek::SeekWork item{};
+                item.first_row = i * lines;
+                item.end_row = i == to ? end : std::min(end, (i + 1) * lines);
+                item.store_from = std::max(first_row, item.first_row);
+                item.row_base = first_row;
+                item.mode = seek::kResumeBand;
+                item.from_point = i == 0 ? 0 : (i - 1) * point_bytes;
+                r.work.push_back(item);
+            }
+            scans.push_back(std::move(r));
+            walk_of.push_back(k);
+        }
+    }
+    run_resume(scans, stream);
+    add_index_counters(from_points, 0, 0, 0);
+    for (size_t k = 0; k < scans.size(); ++k)
+    {
+        Frame& x = s.fr[walks[walk_of[k]].frame];
+        for (const ScanResult& r : scans[k].results) // (the first error from the top of the band down, scan by scan)
+            if (r.errc != kOk && x.errc == CHARLS_JPEGLS_ERRC_SUCCESS)
+                x.errc = static_cast<charls_jpegls_errc>(r.errc);
+        x.done = true;
+    }
+    for (uint32_t i = 0; i < frame_count; ++i)
+        errcs[i] = s.fr[i].errc;
+
+    // ---- the others: the whole frame on the ordinary path into a work area, the band copied out
+    for (uint32_t i = 0; i < frame_count; ++i)
+    {
+        if (!whole[i] || s.fr[i].done)
+            continue;
+        const Frame& x = s.fr[i];
+        const charls_frame_info& f = x.reader.frame_info();
+        const size_t row_bytes = row_bytes_of(scan_spec_of(x.reader));
+        const size_t scans_n = scans_of_frame(x.reader);
+        const size_t frame_bytes = checked_mul(checked_mul(row_bytes, f.height), scans_n);
+        auto* area = static_cast<uint8_t*>(dev::seek_arena(kArenaFrame).ensure(frame_bytes));
+        const charls_jpegls_errc rc = charls_amd_decode_batch_device(1, s.slots + i * stream_pitch_bytes, stream_pitch_bytes, sizes + i, area,
+                                                                     frame_bytes, 0, nullptr, errcs + i, hip_stream);
+        if (rc != CHARLS_JPEGLS_ERRC_SUCCESS)
+            return rc;
+        if (errcs[i] != CHARLS_JPEGLS_ERRC_SUCCESS)
+            continue;
+        for (size_t c = 0; c < scans_n; ++c)
+            hip_check(hipMemcpy2DAsync(bands + i * band_pitch_bytes + strides[i] * row_counts[i] * c, strides[i],
+                                       area + row_bytes * f.height * c + row_bytes * first_rows[i], row_bytes, row_bytes, row_counts[i],
+                                       hipMemcpyDeviceToDevice, stream));
+        hip_check(hipStreamSynchronize(stream));
+    }
+    timings_end();
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}

@@ -448,10 +448,10 @@ charls_jpegls_errc charls_amd_jpegls_decoder_decode_rows(charls_jpegls_decoder* 
 
 int32_t charls_amd_index_counters(uint64_t* out, int32_t capacity)
 {
-    uint64_t v[3];
+    uint64_t v[4];
     index_counters(v);
     int32_t n = 0;
-    for (; out != nullptr && n < capacity && n < 3; ++n)
+    for (; out != nullptr && n < capacity && n < 4; ++n)
         out[n] = v[n];
     return n;
 }

@@ -14,6 +14,7 @@
 #include "common.h"
 #include "scan_engine.h"
 #include "seek_index.h"
+#include "segment_hash.h"
 
 namespace jls {
 
@@ -22,6 +23,7 @@ namespace {
 std::atomic<uint64_t> g_scans_from_points{0};
 std::atomic<uint64_t> g_intervals{0};
 std::atomic<uint64_t> g_fallbacks{0};
+std::atomic<uint64_t> g_launches{0};
 
 constexpr char kMagic[8] = {'J', 'L', 'S', 'S', 'E', 'E', 'K', '\0'};
 
@@ -149,42 +151,56 @@ bool point_in_range(const uint8_t* p, const ScanSpec& s, uint64_t segment_bytes)
 
 uint64_t segment_hash(const uint8_t* p, size_t n) noexcept
 {
-    // A multiply-rotate round per 8 bytes (the shape of xxHash64's round) and murmur3's finaliser.
-    constexpr uint64_t k1 = 0x9E3779B185EBCA87ull, k2 = 0xC2B2AE3D27D4EB4Full;
-    uint64_t h = 0x27D4EB2F165667C5ull ^ (static_cast<uint64_t>(n) * k1);
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8)
-    {
-        uint64_t w = load<uint64_t>(p + i) * k2;
-        w = (w << 31) | (w >> 33);
-        h ^= w * k1;
-        h = ((h << 27) | (h >> 37)) * k1 + 0x85EBCA77C2B2AE63ull;
-    }
-    uint64_t tail = 0;
-    if (i < n)
-        std::memcpy(&tail, p + i, n - i);
-    h ^= tail * k2;
-    h ^= h >> 33;
-    h *= 0xFF51AFD7ED558CCDull;
-    h ^= h >> 33;
-    h *= 0xC4CEB9FE1A85EC53ull;
-    h ^= h >> 33;
-    return h;
+    return segment_hash_bytes(p, n);
 }
 
-void index_counters(uint64_t out[3]) noexcept
+void index_counters(uint64_t out[4]) noexcept
 {
     out[0] = g_scans_from_points.load();
     out[1] = g_intervals.load();
     out[2] = g_fallbacks.load();
+    out[3] = g_launches.load();
+}
+
+void add_index_counters(uint64_t scans_from_points, uint64_t intervals, uint64_t fallbacks, uint64_t launches) noexcept
+{
+    g_scans_from_points.fetch_add(scans_from_points);
+    g_intervals.fetch_add(intervals);
+    g_fallbacks.fetch_add(fallbacks);
+    g_launches.fetch_add(launches);
+}
+
+ScanSpec scan_spec_of(const StreamReader& reader)
+{
+    return current_spec(reader);
+}
+size_t scans_of_frame(const StreamReader& reader) noexcept
+{
+    return scans_of(reader);
+}
+bool same_scan_parameters(const ScanSpec& a, const ScanSpec& b) noexcept
+{
+    return same_parameters(a, b);
+}
+bool seek_spec_eligible(const ScanSpec& spec) noexcept
+{
+    return spec_seek_eligible(spec);
+}
+size_t seek_point_bytes(const ScanSpec& spec) noexcept
+{
+    return point_bytes_of(spec);
+}
+
+size_t index_size_bound(const ScanSpec& first, size_t scans, bool height_from_dnl, uint32_t lines)
+{
+    check_argument(lines > 0);
+    const uint32_t points = !height_from_dnl && spec_seek_eligible(first) ? seek::points_per_scan(first.height, lines) : 0u;
+    return kIndexHeaderBytes + scans * (kIndexScanBytes + points * point_bytes_of(first));
 }
 
 size_t index_size_bound(const StreamReader& reader, uint32_t lines)
 {
-    check_argument(lines > 0);
-    const ScanSpec first = current_spec(reader);
-    const size_t scans = scans_of(reader);
-    return kIndexHeaderBytes + scans * (kIndexScanBytes + expected_points(reader, first, lines) * point_bytes_of(first));
+    return index_size_bound(current_spec(reader), scans_of(reader), reader.height_from_dnl(), lines);
 }
 
 SeekIndex parse_index(const StreamReader& reader, const uint8_t* data, size_t bytes)
@@ -266,6 +282,13 @@ size_t write_index(const StreamReader& reader, const SeekIndex& index, uint8_t* 
         store<uint32_t>(rec + 20, 0);
         if (!s.data.empty())
             std::memcpy(out + at, s.data.data(), s.data.size());
+        // (the kernel writes a point's samples, not the bytes that pad its line to 8: they are zero in the file, whatever the
+        // device buffer held, so that one stream has one index)
+        const size_t point_bytes = point_bytes_of(first);
+        const size_t raw = static_cast<size_t>(planes_of(first)) * (static_cast<size_t>(first.width) + 2) * (first.bits_per_sample > 8 ? 2 : 1);
+        const size_t pad = seek::line_bytes(first.width, planes_of(first), first.bits_per_sample > 8) - raw;
+        for (size_t i = 0; pad != 0 && i < s.points && (i + 1) * point_bytes <= s.data.size(); ++i)
+            std::memset(out + at + i * point_bytes + seek::kLineOff + raw, 0, pad);
         at += s.data.size();
     }
     return total;
@@ -391,6 +414,7 @@ size_t ScanEngine::decode_scan_emit(const ScanSpec& spec, size_t stream_offset, 
     try
     {
         dev::launch_seek_emit(d, d_desc, d_result, 1, d_points, 0, lines, r_->stream);
+        g_launches.fetch_add(1);
     }
     catch (...)
     {
@@ -447,6 +471,7 @@ bool ScanEngine::decode_scan_resumed(const ScanSpec& spec, size_t stream_offset,
     dev::hip_check(hipMemcpyAsync(d_work, work.data(), sizeof(seek::SeekWork) * intervals, hipMemcpyHostToDevice, r_->stream));
     dev::hip_check(hipMemcpyAsync(d_desc, &d, sizeof d, hipMemcpyHostToDevice, r_->stream));
     dev::launch_seek_resume(d, d_desc, d_work, d_results, intervals, d_points, r_->stream);
+    g_launches.fetch_add(1);
     g_intervals.fetch_add(intervals);
     std::vector<ScanResult> results(intervals);
     dev::hip_check(hipMemcpyAsync(results.data(), d_results, sizeof(ScanResult) * intervals, hipMemcpyDeviceToHost, r_->stream));
@@ -504,6 +529,7 @@ void ScanEngine::decode_scan_band(const ScanSpec& spec, size_t stream_offset, ui
     dev::hip_check(hipMemcpyAsync(d_work, work.data(), sizeof(seek::SeekWork) * n, hipMemcpyHostToDevice, r_->stream));
     dev::hip_check(hipMemcpyAsync(d_desc, &d, sizeof d, hipMemcpyHostToDevice, r_->stream));
     dev::launch_seek_resume(d, d_desc, d_work, d_results, n, d_points, r_->stream);
+    g_launches.fetch_add(1);
     g_intervals.fetch_add(n);
     std::vector<ScanResult> results(n);
     dev::hip_check(hipMemcpyAsync(results.data(), d_results, sizeof(ScanResult) * n, hipMemcpyDeviceToHost, r_->stream));

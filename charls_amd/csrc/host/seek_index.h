@@ -16,12 +16,11 @@
 #include <cstdint>
 #include <vector>
 
+#include "scan_engine.h"
 #include "stream_reader.h"
 
 namespace jls {
 
-class ScanEngine;
-struct ScanSpec;
 
 constexpr uint32_t kIndexVersion = 1;
 constexpr size_t kIndexHeaderBytes = 72;
@@ -74,7 +73,19 @@ void decode_rows(const StreamReader& reader, ScanEngine& engine, const SeekIndex
                  uint8_t* destination, size_t destination_size, size_t stride);
 
 // charls_amd_index_counters: scans decoded from seek points, intervals launched, scans decoded from the top after their
-// index did not hold.
-void index_counters(uint64_t out[3]) noexcept;
+// index did not hold, launches of the seek kernels.
+void index_counters(uint64_t out[4]) noexcept;
+
+// ---- what the batch calls of part 2c (batch_index.cpp) share with part 1
+// The parameters of the scan whose header `reader` has read (the index describes a frame by its first scan's).
+ScanSpec scan_spec_of(const StreamReader& reader);
+size_t scans_of_frame(const StreamReader& reader) noexcept;
+bool same_scan_parameters(const ScanSpec& a, const ScanSpec& b) noexcept;
+// The kernels' conditions on the parameters alone (where the rows lie is the caller's to check).
+bool seek_spec_eligible(const ScanSpec& spec) noexcept;
+size_t seek_point_bytes(const ScanSpec& spec) noexcept;
+// index_size_bound for a frame of `scans` scans with this first scan.
+size_t index_size_bound(const ScanSpec& first, size_t scans, bool height_from_dnl, uint32_t lines);
+void add_index_counters(uint64_t scans_from_points, uint64_t intervals, uint64_t fallbacks, uint64_t launches) noexcept;
 
 } // namespace jls

@@ -458,8 +458,60 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_jpegls_decoder_decode_rows(charls_j
                                                                         size_t destination_size_bytes, uint32_t stride);
 /* What the seek-point index did since the library was loaded (process-wide): out[0] scans decoded from seek points (full
  * decodes and bands), out[1] wavefronts launched from the index (intervals and bands), out[2] scans whose index did not
- * hold (hash or chain check) and that were decoded from the top.  Returns the number of values written (3 at most). */
+ * hold (hash or chain check) and that were decoded from the top, out[3] launches of the seek kernels (the one that writes
+ * seek points and the one that starts from them; a batch call of part 2c is one launch per group of scans, not one per
+ * frame).  Returns the number of values written (4 at most; a caller that asks for 3 gets the first three). */
 CHARLS_AMD_API int32_t charls_amd_index_counters(uint64_t* out, int32_t capacity);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Part 2c -- the seek-point index in the batch API: streams, frames and bands are DEVICE memory as in part 2, indexes are
+ * HOST memory (they are sidecars that come from and go to storage; checking one needs no GPU).  Index f lies at
+ * indexes + f * index_pitch_bytes; index_sizes is a HOST array of frame_count elements.
+ *
+ * The contract per frame is part 1's: frame f gets the pixels, the index bytes and the errc that a fresh part-1 decoder
+ * gives for the same stream -- set_source_buffer(stream f, sizes[f]), read_header, set_index where there is one, then
+ * decode_to_buffer_and_index, decode_to_buffer or decode_rows --, errcs[f] being the first code of that sequence that is
+ * not success.  In particular: an index_pitch_bytes below the frame's get_index_size is invalid_argument_size and nothing
+ * of that frame is decoded; an index set_index would refuse is invalid_argument; a full decode through an index is kept
+ * only when every interval ends in exactly the next seek point's state, and is otherwise done again from the top
+ * (charls_amd_index_counters [2]); a band trusts an index whose segment hash matches and is invalid_argument otherwise;
+ * frames that get no seek points (restart intervals, scans the exact decoder does not take, a height from DNL, a scan
+ * whose parameters differ from the first scan's) go the ordinary way.  16-bit frames whose rows would start at odd addresses
+ * (an odd d_frames / d_bands, pitch or stride) go the ordinary way too and get an index without seek points.
+ * One frame's failure never changes another frame's result, and nothing is written outside a frame's own extent of
+ * d_frames, d_bands or indexes.  The return value, hip_stream, stride, params_out and the 16-byte readability rule for
+ * d_streams are those of charls_amd_decode_batch_device; the frames of a call may differ in geometry and coding
+ * parameters.  The segment hashes are computed on the device: no stream is copied to the host.
+ *
+ * All scans of a call that share the seek kernels' specialisation (sample width, components per pixel) are ONE launch:
+ * building runs one launch per group and scan ordinal (scan c + 1 starts where scan c ended); decoding through indexes
+ * and decoding bands run one launch per group for all scans of all frames (the index names every segment's length).
+ * Frames whose chain check fails and frames without seek points are decoded in the same call by the ordinary launches.
+ *
+ * index_size_bound: what get_index_size returns for a stream with these parameters (an upper bound of the index for
+ *   K = lines_per_seek_point >= 1); needs no GPU.  encoding_options is not looked at.
+ * decode_batch_device_and_index: charls_amd_decode_batch_device that also builds every frame's index; index_sizes[f] is
+ *   its size, 0 where the frame failed (nothing is written to its slot then).
+ * decode_batch_device_indexed: charls_amd_decode_batch_device through indexes; index_sizes[f] == 0: frame f has no index
+ *   and decodes the ordinary way.  Worth it for small batches: see INTEGRATION.md.
+ * decode_rows_batch_device: rows [first_rows[f], first_rows[f] + row_counts[f]) of frame f in decode_rows' layout at
+ *   d_bands + f * band_pitch_bytes (a band_pitch_bytes below what the band needs: invalid_argument_size for that frame).
+ *   index_sizes[f] == 0: from the top.  Frames without seek points, and planar frames without an index, are decoded whole
+ *   into a work area on the ordinary path and the band is copied out (damage below the band is then reported too). */
+CHARLS_AMD_API charls_jpegls_errc charls_amd_index_size_bound(const charls_amd_codec_params* params,
+                                                              uint32_t lines_per_seek_point, size_t* bytes);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_device_and_index(
+    uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes, const uint64_t* sizes, void* d_frames,
+    size_t frame_pitch_bytes, uint32_t stride, uint32_t lines_per_seek_point, void* indexes, size_t index_pitch_bytes,
+    uint64_t* index_sizes, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_device_indexed(
+    uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes, const uint64_t* sizes, const void* indexes,
+    size_t index_pitch_bytes, const uint64_t* index_sizes, void* d_frames, size_t frame_pitch_bytes, uint32_t stride,
+    charls_amd_codec_params* params_out, charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_rows_batch_device(
+    uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes, const uint64_t* sizes, const void* indexes,
+    size_t index_pitch_bytes, const uint64_t* index_sizes, const uint32_t* first_rows, const uint32_t* row_counts,
+    void* d_bands, size_t band_pitch_bytes, uint32_t stride, charls_jpegls_errc* errcs, void* hip_stream);
 
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */

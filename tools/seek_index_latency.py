@@ -1,7 +1,13 @@
 """The seek-point index on ONE 4096 x 4096 8-bit frame through the host-pointer C ABI (PCIe inclusive), best and median of N
 calls: plain decode, decode + index build, decode through an index for K = 32, 64, 128, a 64-row band from the middle
 with and without an index, and the index's size as a share of the stream.  Streams: the tulips image tiled, and the
-synthetic frame of tools/one_frame_latency.py.  Run on the GPU box: python tools/seek_index_latency.py [--calls 5]"""
+synthetic frame of tools/one_frame_latency.py.  Run on the GPU box: python tools/seek_index_latency.py [--calls 5]
+
+--batch: the same index through the device-memory batch API (charls_amd.h part 2c), every figure beside the part-1 or
+plain-batch figure of the same run: building N indexes in one call against N x one part-1 build, decoding N frames through
+K = 64 indexes against charls_amd_decode_batch_device, 64-row bands at K = 16 from N frames, and the GPU time of the
+segment-hash launches (charls_amd_last_timings [1]).  The N slots hold N copies of one stream: frames are independent, so
+the times are those of N different streams of that size.  --frames / --build-frames choose the N."""
 import argparse
 import os
 import statistics
@@ -17,6 +23,11 @@ import common  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--calls", type=int, default=5)
 ap.add_argument("--size", type=int, default=4096)
+ap.add_argument("--batch", action="store_true")
+ap.add_argument("--frames", type=int, nargs="*", default=[1, 4, 16, 64, 256, 1024])
+ap.add_argument("--build-frames", type=int, nargs="*", default=[1, 16, 256, 1024])
+ap.add_argument("--band-frames", type=int, nargs="*", default=[1, 64, 1024])
+ap.add_argument("--images", nargs="*", default=["tulips_tiled", "synthetic"])
 args = ap.parse_args()
 lib = capi.load_product()
 
@@ -36,6 +47,81 @@ def line(what, best, median, extra=""):
 
 n = args.size
 frames = {"tulips_tiled": common.tulips_tiled(n, n, 0), "synthetic": synth.frame_numpy(n, n, seed=2, bits=8)}
+frames = {name: img for name, img in frames.items() if name in args.images}
+
+
+def batch_mode():
+    import numpy as np
+    import torch
+    from charls_amd import batch
+
+    def gpu_clock(fn, calls):
+        times, hashes, out = [], [], None
+        for _ in range(calls):
+            torch.cuda.synchronize()
+            a = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - a)
+            hashes.append(batch.last_timings(lib)[1])
+        return min(times), statistics.median(times), min(hashes), out
+
+    most = max(args.frames + args.build_frames + args.band_frames)
+    mpix = n * n / 1e6
+    for name, img in frames.items():
+        jls = lib.encode(img, width=n, height=n, bits_per_sample=8)
+        pitch = (len(jls) + 255) & ~255
+        print(f"{name} {n} x {n} 8-bit: {len(jls)} B, slots of {pitch} B", flush=True)
+        one = torch.zeros(pitch, dtype=torch.uint8)
+        one[:len(jls)] = torch.frombuffer(bytearray(jls), dtype=torch.uint8)
+        d_streams = one.cuda().repeat(most, 1).contiguous()
+        sizes = np.full(most, len(jls), dtype=np.uint64)
+        out = torch.empty((most, n * n), dtype=torch.uint8, device="cuda")
+        want = torch.from_numpy(img.reshape(-1)).cuda()
+        # ---- build
+        a = time.perf_counter()
+        _, px, part1 = lib.decode_with_index(jls, 64)
+        part1_build = time.perf_counter() - a
+        assert px.tobytes() == img.tobytes()
+        print(f"  part-1 decode + index build (K=64): {part1_build:.3f} s = {mpix / part1_build:.2f} MPix/s", flush=True)
+        bound = batch.index_size_bound(n, n, lines_per_seek_point=64, lib=lib)
+        for N in args.build_frames:
+            best, _, hash_ms, (_, errcs, built) = gpu_clock(
+                lambda: batch.decode_batch_and_index(d_streams[:N], sizes[:N], out[:N], 64, index_pitch=bound, lib=lib), 1)
+            assert (errcs == 0).all() and built[0] == part1 and built[-1] == part1 and torch.equal(out[N - 1], want)
+            print(f"  build N={N:<5} one call {best:8.3f} s = {N * mpix / best:9.1f} MPix/s   N x part 1 = {N * part1_build:9.1f} s"
+                  f"   hash launches {hash_ms:.2f} ms", flush=True)
+        # ---- indexed decode against the plain batch decoder
+        index16 = lib.decode_with_index(jls, 16)[2]
+        for N in args.frames:
+            out[:N].zero_()
+            best, med, hash_ms, (_, errcs) = gpu_clock(lambda: batch.decode_batch_indexed(d_streams[:N], sizes[:N], [part1] * N, out[:N], lib=lib),
+                                                       args.calls)
+            assert (errcs == 0).all() and torch.equal(out[N - 1], want)
+            out[:N].zero_()
+            pbest, pmed, _, (_, errcs, _) = gpu_clock(lambda: batch.decode_batch(d_streams[:N], sizes[:N], out[:N], lib=lib), args.calls)
+            assert (errcs == 0).all() and torch.equal(out[N - 1], want)
+            print(f"  decode N={N:<5} indexed K=64 best {best * 1e3:9.1f} ms median {med * 1e3:9.1f} ms = {N * mpix / best:9.1f} MPix/s"
+                  f" (hash launch {hash_ms:.2f} ms)   plain batch best {pbest * 1e3:9.1f} ms median {pmed * 1e3:9.1f} ms = {N * mpix / pbest:9.1f} MPix/s",
+                  flush=True)
+        # ---- 64-row bands
+        first = n // 2 - 32
+        band_want = want[first * n:(first + 64) * n]
+        bands = torch.empty((max(args.band_frames), 64 * n), dtype=torch.uint8, device="cuda")
+        b1, m1, band = clock(lambda: lib.decode_rows(jls, first, 64, index=index16), args.calls)
+        print(f"  part-1 64-row band, index K=16: best {b1:.1f} ms median {m1:.1f} ms", flush=True)
+        for N in args.band_frames:
+            bands[:N].zero_()
+            best, med, hash_ms, errcs = gpu_clock(lambda: batch.decode_rows_batch(d_streams[:N], sizes[:N], [index16] * N, [first] * N, [64] * N,
+                                                                                bands[:N], lib=lib), args.calls)
+            assert (errcs == 0).all() and torch.equal(bands[N - 1], band_want)
+            print(f"  bands N={N:<5} K=16 best {best * 1e3:9.1f} ms median {med * 1e3:9.1f} ms, of which the hash launch {hash_ms:.2f} ms"
+                  f" = {100 * hash_ms / (best * 1e3):.0f}%   N x part 1 = {N * b1:9.1f} ms", flush=True)
+
+
+if args.batch:
+    batch_mode()
+    sys.exit(0)
 for name, img in frames.items():
     jls = lib.encode(img, width=n, height=n, bits_per_sample=8)
     print(f"{name} {n} x {n} 8-bit: {len(jls)} B", flush=True)
