@@ -76,6 +76,15 @@ def _bind(lib):
     l.charls_amd_decode_rows_batch_device.restype = C.c_int32
     l.charls_amd_index_counters.argtypes = [u64p, C.c_int32]
     l.charls_amd_index_counters.restype = C.c_int32
+    l.charls_amd_pack_streams_device.argtypes = [C.c_uint32, C.c_void_p, C.c_size_t, u64p, C.c_void_p, C.c_size_t, C.c_uint32, u64p,
+                                                 C.c_void_p]
+    l.charls_amd_pack_streams_device.restype = C.c_int32
+    l.charls_amd_encode_batch_device_packed.argtypes = [C.POINTER(CodecParams), C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                        C.c_void_p, C.c_size_t, C.c_uint32, C.c_size_t, u64p, u64p, i32p, C.c_void_p]
+    l.charls_amd_encode_batch_device_packed.restype = C.c_int32
+    l.charls_amd_decode_batch_device_packed.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                        C.POINTER(CodecParams), i32p, C.c_void_p]
+    l.charls_amd_decode_batch_device_packed.restype = C.c_int32
     l._batch_bound = True
     return l
 
@@ -282,6 +291,100 @@ def decode_rows_batch(streams, sizes, indexes, first_rows, row_counts, bands, *,
     if rc != 0:
         raise capi.JpegLSError(rc, "charls_amd_decode_rows_batch_device")
     return errcs
+
+
+# ---- packed streams (charls_amd.h part 2d): one device buffer, a host table of offsets ------------------------------------
+
+@dataclass
+class PackedBatch:
+    packed: "torch.Tensor"   # 1-D uint8 on the device; frame f's .jls is packed[offsets[f]:offsets[f] + sizes[f]]
+    offsets: np.ndarray      # uint64, host, frames + 1 elements; offsets[-1] is the total
+    sizes: np.ndarray        # uint64, host
+    errcs: np.ndarray        # int32, host (None from pack_streams)
+
+
+def pack_streams(streams, sizes, *, alignment=1, packed=None, capacity=None, lib=None) -> PackedBatch:
+    """charls_amd_pack_streams_device: the (F, pitch) slot tensor of encode_batch into the packed form.  packed: a 1-D uint8
+    device tensor to fill (by default one of exactly the total is made); capacity: what the call may use of it."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert streams.is_cuda and streams.is_contiguous()
+    count = streams.shape[0]
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    assert len(sizes) == count
+    if packed is None:
+        total, step = 0, max(int(alignment), 1)  # (an alignment the call refuses: it says so itself)
+        for s in sizes:
+            total = -(-(total + int(s)) // step) * step
+        packed = torch.empty(max(total, 16), dtype=torch.uint8, device=streams.device)
+        if capacity is None:
+            capacity = total
+    assert packed.is_cuda and packed.is_contiguous()
+    if capacity is None:
+        capacity = packed.numel()
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    stream = torch.cuda.current_stream(streams.device).cuda_stream
+    rc = l.charls_amd_pack_streams_device(count, streams.data_ptr(), streams.shape[1] if streams.dim() == 2 else 0,
+                                          sizes.ctypes.data_as(C.POINTER(C.c_uint64)), packed.data_ptr(), int(capacity), alignment,
+                                          offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_pack_streams_device")
+    return PackedBatch(packed, offsets, sizes, None)
+
+
+def encode_batch_packed(frames, packed, *, alignment=1, max_stream_bytes=0, capacity=None, bits_per_sample=8, component_count=1,
+                        interleave_mode=0, near_lossless=0, color_transformation=0, preset=(0, 0, 0, 0, 0), encoding_options=0,
+                        restart_interval=0, lib=None) -> PackedBatch:
+    """charls_amd_encode_batch_device_packed: encode_batch without slots -- the streams go back to back into `packed` (a 1-D
+    uint8 device tensor; capacity: what the call may use of it, by default all).  frames as for encode_batch."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert frames.is_cuda and frames.is_contiguous() and packed.is_cuda and packed.is_contiguous()
+    count = frames.shape[0]
+    if component_count == 1 or interleave_mode == 0:
+        height, width = frames.shape[-2], frames.shape[-1]
+    else:
+        height, width = frames.shape[1], frames.shape[2]
+    frame_pitch = frames[0].numel() * frames.element_size() if count else 0
+    p = CodecParams(capi.FrameInfo(width, height, bits_per_sample, component_count), near_lossless, interleave_mode,
+                    color_transformation, capi.PcParameters(*preset), encoding_options, restart_interval)
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    sizes = np.zeros(count, dtype=np.uint64)
+    errcs = np.zeros(count, dtype=np.int32)
+    stream = torch.cuda.current_stream(frames.device).cuda_stream
+    rc = l.charls_amd_encode_batch_device_packed(C.byref(p), count, frames.data_ptr(), frame_pitch, 0, packed.data_ptr(),
+                                                 packed.numel() if capacity is None else int(capacity), alignment, int(max_stream_bytes),
+                                                 offsets.ctypes.data_as(C.POINTER(C.c_uint64)), sizes.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_encode_batch_device_packed")
+    return PackedBatch(packed, offsets, sizes, errcs)
+
+
+def decode_batch_packed(packed, offsets, sizes, out, *, stride=0, frame_pitch=None, lib=None):
+    """charls_amd_decode_batch_device_packed: decode_batch with frame f's stream at packed[offsets[f]:offsets[f] + sizes[f]]
+    (offsets: host uint64, at least len(sizes) elements, any order).  Returns (params, errcs, gpu_ms)."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert packed.is_cuda and packed.is_contiguous() and out.is_cuda
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    count = len(sizes)
+    assert len(offsets) >= count
+    errcs = np.zeros(count, dtype=np.int32)
+    p = CodecParams()
+    if frame_pitch is None:
+        frame_pitch = out[0].numel() * out.element_size() if count else 0
+    stream = torch.cuda.current_stream(packed.device).cuda_stream
+    rc = l.charls_amd_decode_batch_device_packed(count, packed.data_ptr(), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 sizes.ctypes.data_as(C.POINTER(C.c_uint64)), out.data_ptr(), frame_pitch, stride,
+                                                 C.byref(p), errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_decode_batch_device_packed")
+    return p, errcs, last_timings(lib)
 
 
 def set_workspace_limit(nbytes: int, lib=None):

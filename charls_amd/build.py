@@ -27,6 +27,7 @@ SOURCES = [
     "device/launch_group_encode_u16.hip",
     "device/seek_launch.hip",
     "device/segment_hash.hip",
+    "device/pack_streams.hip",
     "host/stream_reader.cpp",
     "host/scan_engine.cpp",
     "host/encoder_api.cpp",
@@ -35,6 +36,7 @@ SOURCES = [
     "host/misc_api.cpp",
     "host/batch_api.cpp",
     "host/batch_index.cpp",
+    "host/batch_packed.cpp",
     "host/multi_device.cpp",
 ]
 

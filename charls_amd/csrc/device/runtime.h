@@ -147,6 +147,9 @@ uint64_t workspace_limit() noexcept;          // as set (0: the default rule)
 void release_shared_work_areas() noexcept;    // the shared sets of the host-pointer ABI's merged launches, all devices (a launch that runs finishes first)
 size_t shared_work_area_bytes() noexcept;     // what they hold
 DeviceBuffer& plane_arena(); // the calling thread's private stream buffers of the planar batch encoder (a work area)
+// The calling thread's staging slots of charls_amd_encode_batch_device_packed (host/batch_packed.cpp): a pass of frames is
+// coded into them and packed from them (a work area: counted by work_area_bytes, freed by release_work_areas).
+DeviceBuffer& pack_arena();
 // The calling thread's buffers of the seek-point index's batch calls (host/batch_index.cpp): seek points, work items, descs,
 // results, hash jobs (work areas: counted by work_area_bytes, freed by release_work_areas).
 constexpr int kSeekArenas = 6;

@@ -577,11 +577,11 @@ struct PipelineLanes
 constexpr int kIntervalArenas = 8;
 struct WorkAreas
 {
-    DeviceBuffer pipeline, plane, interval[kIntervalArenas], seek[kSeekArenas];
+    DeviceBuffer pipeline, plane, pack, interval[kIntervalArenas], seek[kSeekArenas];
     PipelineLanes lanes;
     size_t bytes() const noexcept
     {
-        size_t total = pipeline.capacity() + plane.capacity();
+        size_t total = pipeline.capacity() + plane.capacity() + pack.capacity();
         for (const DeviceBuffer& b : interval)
             total += b.capacity();
         for (const DeviceBuffer& b : seek)
@@ -592,6 +592,7 @@ struct WorkAreas
     {
         pipeline.release();
         plane.release();
+        pack.release();
         for (DeviceBuffer& b : interval)
             b.release();
         for (DeviceBuffer& b : seek)
@@ -1475,6 +1476,11 @@ void launch_encode(const ScanDesc& proto, ScanDesc* d_descs, ScanResult* d_resul
 DeviceBuffer& plane_arena()
 {
     return areas().plane;
+}
+
+DeviceBuffer& pack_arena()
+{
+    return areas().pack;
 }
 
 DeviceBuffer& seek_arena(int which)

@@ -13,6 +13,7 @@
 
 #include "../device/knobs.h"
 #include "../device/runtime.h"
+#include "batch_streams.h"
 #include "common.h"
 #include "preset.h"
 #include "stream_reader.h"
@@ -368,19 +369,13 @@ catch (...)
     return current_exception_to_errc();
 }
 
-extern "C" charls_jpegls_errc charls_amd_decode_batch_device(uint32_t frame_count, const void* d_streams,
-                                                             size_t stream_pitch_bytes, const uint64_t* sizes,
-                                                             void* d_frames, size_t frame_pitch_bytes,
-                                                             uint32_t stride_arg, charls_amd_codec_params* params_out,
-                                                             charls_jpegls_errc* errcs, void* hip_stream)
-try
+// The batch decoder behind charls_amd_decode_batch_device (slots: stream_at[i] = i * pitch) and
+// charls_amd_decode_batch_device_packed (batch_packed.cpp: stream_at = the caller's offset table): frame i's stream is the
+// sizes[i] bytes at d_streams + stream_at[i].  frame_count >= 1, the pointers are checked by the entry points.
+void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, const uint64_t* stream_at, const uint64_t* sizes,
+                               void* d_frames, size_t frame_pitch_bytes, uint32_t stride_arg,
+                               charls_amd_codec_params* params_out, charls_jpegls_errc* errcs, void* hip_stream)
 {
-    check_pointer(sizes);
-    check_pointer(errcs);
-    if (frame_count == 0)
-        return CHARLS_JPEGLS_ERRC_SUCCESS;
-    check_pointer(d_streams);
-    check_pointer(d_frames);
     dev::require_device();
     auto stream = static_cast<hipStream_t>(hip_stream);
     const auto* slots = static_cast<const uint8_t*>(d_streams);
@@ -408,7 +403,7 @@ try
         x.window.resize(n);
         x.window_base = base;
         if (n)
-            hip_check(hipMemcpyAsync(x.window.data(), slots + i * stream_pitch_bytes + base, n, hipMemcpyDeviceToHost, stream));
+            hip_check(hipMemcpyAsync(x.window.data(), slots + stream_at[i] + base, n, hipMemcpyDeviceToHost, stream));
     };
     // the same for many frames at once (bases[k] is the offset of frame which[k]'s window): one gather on the device, one copy
     dev::DeviceBuffer d_specs, d_windows;
@@ -422,7 +417,7 @@ try
         {
             const uint32_t i = which[k];
             const size_t avail = bases[k] < sizes[i] ? static_cast<size_t>(sizes[i]) - bases[k] : 0;
-            specs[k] = WindowSpec{static_cast<uint64_t>(i) * stream_pitch_bytes + bases[k],
+            specs[k] = WindowSpec{stream_at[i] + bases[k],
                                   static_cast<uint32_t>(std::min(kWindow, avail)), 0};
         }
         d_specs.ensure(sizeof(WindowSpec) * n);
@@ -473,16 +468,10 @@ try
         }
     };
 
-    if (stream_pitch_bytes == 0)
-        raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
     {
         std::vector<uint32_t> all(frame_count);
         for (uint32_t i = 0; i < frame_count; ++i)
-        {
-            if (sizes[i] > stream_pitch_bytes)
-                raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
             all[i] = i;
-        }
         fetch_many(fr, all, std::vector<size_t>(frame_count, 0));
     }
     for (uint32_t i = 0; i < frame_count; ++i)
@@ -522,7 +511,7 @@ try
                                x.reader.parameters().restart_interval);
         d.pixels = frames + i * frame_pitch_bytes + x.plane_offset;
         d.pixel_stride = stride;
-        d.stream = const_cast<uint8_t*>(slots) + i * stream_pitch_bytes + x.cursor;
+        d.stream = const_cast<uint8_t*>(slots) + stream_at[i] + x.cursor;
         d.stream_capacity = sizes[i] - x.cursor;
         d.line_scratch = reinterpret_cast<uint16_t*>(scratch_total); // placed by run_scans
         scratch_total += dev::line_scratch_samples(f.width, ilv, static_cast<int32_t>(nc)) * sizeof(uint16_t);
@@ -643,8 +632,7 @@ try
             for (size_t q = 0; q < n; ++q)
             {
                 const uint32_t i = plans[need[q]].frame;
-                search[q] = MarkerSearch{static_cast<uint64_t>(i) * stream_pitch_bytes + plans[need[q]].starts.back(),
-                                         static_cast<uint64_t>(i) * stream_pitch_bytes + sizes[i]};
+                search[q] = MarkerSearch{stream_at[i] + plans[need[q]].starts.back(), stream_at[i] + sizes[i]};
             }
             d_search.ensure(sizeof(MarkerSearch) * n);
             d_found.ensure(sizeof(unsigned long long) * n);
@@ -662,7 +650,7 @@ try
                     p.ok = false;
                     continue;
                 }
-                p.marker_at.push_back(static_cast<size_t>(found[q] - static_cast<uint64_t>(p.frame) * stream_pitch_bytes));
+                p.marker_at.push_back(static_cast<size_t>(found[q] - stream_at[p.frame]));
                 which.push_back(p.frame);
                 bases.push_back(p.marker_at.back());
             }
@@ -843,6 +831,33 @@ try
     t.values[0] = scan_ms;
     t.values[1] = scan_ms;
     t.count = 2;
+}
+
+extern "C" charls_jpegls_errc charls_amd_decode_batch_device(uint32_t frame_count, const void* d_streams,
+                                                             size_t stream_pitch_bytes, const uint64_t* sizes,
+                                                             void* d_frames, size_t frame_pitch_bytes,
+                                                             uint32_t stride_arg, charls_amd_codec_params* params_out,
+                                                             charls_jpegls_errc* errcs, void* hip_stream)
+try
+{
+    check_pointer(sizes);
+    check_pointer(errcs);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    check_pointer(d_streams);
+    check_pointer(d_frames);
+    dev::require_device();
+    if (stream_pitch_bytes == 0)
+        raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+    std::vector<uint64_t> stream_at(frame_count);
+    for (uint32_t i = 0; i < frame_count; ++i)
+    {
+        if (sizes[i] > stream_pitch_bytes)
+            raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+        stream_at[i] = static_cast<uint64_t>(i) * stream_pitch_bytes;
+    }
+    decode_batch_streams(frame_count, d_streams, stream_at.data(), sizes, d_frames, frame_pitch_bytes, stride_arg, params_out, errcs,
+                         hip_stream);
     return CHARLS_JPEGLS_ERRC_SUCCESS;
 }
 catch (...)

@@ -513,6 +513,56 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_rows_batch_device(
     size_t index_pitch_bytes, const uint64_t* index_sizes, const uint32_t* first_rows, const uint32_t* row_counts,
     void* d_bands, size_t band_pitch_bytes, uint32_t stride, charls_jpegls_errc* errcs, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Part 2d -- PACKED streams in the batch API: the streams of a batch back to back in ONE device buffer with a HOST table
+ * of offsets -- the form files, archives, DICOM multi-frame pixel data and charls_amd_gather hold them in -- instead of
+ * fixed-pitch slots.  Frame f's .jls is the sizes[f] bytes at d_packed + offsets[f].  `offsets`, `sizes` and `errcs` are HOST
+ * arrays; the return value, hip_stream, stride and params_out are those of part 2.  New entry points beside the slot
+ * calls: those, the indexed calls of part 2c and the multi-device calls of part 2b stay on slots.
+ *
+ * The offset rule (pack_streams, encode_batch_device_packed): offsets[0] = 0 and offsets[f + 1] = offsets[f] + sizes[f]
+ * rounded up to `offset_alignment`, a power of two in [1, 4096] (anything else: invalid_argument for the whole call, before
+ * anything is done).  The alignment is of the offset within d_packed, not of the address.  The bytes of the gaps are
+ * zero.  A frame with sizes[f] == 0 -- a frame that failed -- takes no room, as in charls_amd_gather.  offsets has
+ * frame_count + 1 elements; offsets[frame_count] is the total.
+ *
+ * pack_streams_device: the slot array of charls_amd_encode_batch_device (frame f at d_streams + f * stream_pitch_bytes,
+ *   sizes[f] bytes) into the packed form, with one launch of a copy kernel that takes any alignment on either side.  A
+ *   sizes[f] above stream_pitch_bytes, or a total beyond packed_capacity_bytes, is invalid_argument_size and nothing is
+ *   written, neither to d_packed nor to offsets.  d_streams and d_packed must not overlap.  The copy loads whole 16-byte
+ *   aligned groups: the readability rule of part 2 holds for d_streams.
+ * encode_batch_device_packed: frame f gets exactly the bytes and the errc charls_amd_encode_batch_device gives it with
+ *   stream_pitch_bytes = max_stream_bytes (0 = charls_jpegls_encoder_get_estimated_destination_size of the frame; too small
+ *   a value is destination_too_small for the frames it is too small for, as there), placed at offsets[f] under the rule
+ *   above with sizes[f] == 0 for every frame whose errc is not success.  The capacity: a frame whose end offsets[f] +
+ *   sizes[f] lies beyond packed_capacity_bytes gets destination_too_small, and so does EVERY frame after it; nothing of
+ *   them is written and they take no room.  Nothing is written at or beyond packed_capacity_bytes (the zeros behind the
+ *   last frame that fits stop there, though offsets[f + 1] follows the rule).  The caller provides no slots: the call codes
+ *   passes of frames into staging slots of its own and packs every pass with one launch.  The staging slots are one more
+ *   work area of the calling thread (at most a quarter of what its work areas may hold, see
+ *   charls_amd_set_workspace_limit; counted by charls_amd_work_area_bytes, freed by charls_amd_release_work_areas); when
+ *   not even one slot of max_stream_bytes can be had the call returns not_enough_memory.
+ * decode_batch_device_packed: charls_amd_decode_batch_device with frame f's stream at d_packed + offsets[f] (offsets has
+ *   frame_count elements): the same pixels, params_out and errcs, for frames of mixed geometry and coding parameters, for
+ *   damaged and truncated streams; one frame's failure never changes another's.  The offsets may come in any order, at
+ *   any alignment, and may name the same bytes twice (streams are only read).  offsets[f] + sizes[f] that overflows is
+ *   invalid_argument_size for the whole call.  Readability: the allocation that holds d_packed must be readable from the
+ *   16-byte boundary at or before the lowest offset to the one at or after the highest end (any hipMalloc'ed buffer is).
+ * ---------------------------------------------------------------------------------------------------------------- */
+CHARLS_AMD_API charls_jpegls_errc charls_amd_pack_streams_device(uint32_t frame_count, const void* d_streams,
+                                                                 size_t stream_pitch_bytes, const uint64_t* sizes,
+                                                                 void* d_packed, size_t packed_capacity_bytes,
+                                                                 uint32_t offset_alignment, uint64_t* offsets, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_encode_batch_device_packed(
+    const charls_amd_codec_params* params, uint32_t frame_count, const void* d_frames, size_t frame_pitch_bytes, uint32_t stride,
+    void* d_packed, size_t packed_capacity_bytes, uint32_t offset_alignment, size_t max_stream_bytes, uint64_t* offsets,
+    uint64_t* sizes, charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_device_packed(uint32_t frame_count, const void* d_packed,
+                                                                        const uint64_t* offsets, const uint64_t* sizes,
+                                                                        void* d_frames, size_t frame_pitch_bytes, uint32_t stride,
+                                                                        charls_amd_codec_params* params_out,
+                                                                        charls_jpegls_errc* errcs, void* hip_stream);
+
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */
 CHARLS_AMD_API charls_jpegls_errc charls_amd_set_encode_engine(int32_t engine);
