@@ -103,45 +103,85 @@ def check_no_scratch(objs: list[str]) -> list[dict]:
     return table
 
 
+def _start_compile(cmd: list[str]):
+    """One translation unit (the only place the compiler is started: tests/test_build_flags_cpu.py replaces it)."""
+    return subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+
+
+def _link(cmd: list[str]) -> None:
+    subprocess.check_call(cmd)
+
+
+def _read_stamp(path: str) -> str | None:
+    try:
+        with open(path) as f:
+            return f.read()
+    except OSError:
+        return None
+
+
+def _write_stamp(path: str, text: str) -> None:
+    with open(path, "w") as f:
+        f.write(text)
+
+
+def _stamp_of(obj: str) -> str:
+    return obj + ".flags"
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
-    if not force and os.path.exists(OUT) and os.path.exists(OUT_ALIAS) and os.path.getmtime(OUT) >= _newest_source():
+    extra = os.environ.get("CHARLS_AMD_CXXFLAGS", "").split()  # (e.g. -DJLS_PHASE_CLOCKS, tools/phase_clocks.py)
+    options = ["--offload-arch=" + OFFLOAD_ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wextra",
+               "-Wno-unused-parameter", *extra]
+    # What an object (and the library linked from the objects) was built with, kept in a stamp beside it: an object whose
+    # stamp differs is compiled again, so that a build with CHARLS_AMD_CXXFLAGS (an instrumented build, one side of an A/B)
+    # never leaves its objects in the next plain build.  The include directories are not part of it: they move with the tree.
+    stamp = " ".join(options) + "\n"
+    if not force and os.path.exists(OUT) and os.path.exists(OUT_ALIAS) and os.path.getmtime(OUT) >= _newest_source() \
+            and _read_stamp(_stamp_of(OUT)) == stamp:
         return OUT
     os.makedirs(OUT_DIR, exist_ok=True)
     obj_dir = os.path.join(OUT_DIR, "obj")
     os.makedirs(obj_dir, exist_ok=True)
-    common = ["--offload-arch=" + OFFLOAD_ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wextra",
-              "-Wno-unused-parameter", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-              *os.environ.get("CHARLS_AMD_CXXFLAGS", "").split()]  # (e.g. -DJLS_PHASE_CLOCKS, tools/phase_clocks.py)
+    common = [*options, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
     objs = []
     procs = []
-    # An object is compiled again when anything it can include is newer: the device units include device/ only, the host
-    # units host/, the headers of device/ and the public header (a change to a kernel does not recompile the facade, a change
-    # to the facade not the kernels -- the five device units take minutes).  CHARLS_AMD_CXXFLAGS always recompile.
+    # An object is compiled again when anything it can include is newer: the device units include device/, host/common.h
+    # (through runtime.h) and the public header it includes; the host units host/, the headers of device/ and the public
+    # header (a change to a kernel does not recompile the facade, a change to the facade's sources not the kernels -- the
+    # five device units take minutes).  `force` compiles everything.
     def newest(paths):
         return max(os.path.getmtime(f) for f in paths if os.path.isfile(f))
     device_files = glob.glob(os.path.join(CSRC, "device", "*"))
+    public_header = os.path.join(ROOT, "include", "charls_amd.h")
+    device_deps = device_files + [os.path.join(CSRC, "host", "common.h"), public_header, __file__]
     host_deps = glob.glob(os.path.join(CSRC, "host", "*")) + [f for f in device_files if f.endswith(".h")] + \
-        [os.path.join(ROOT, "include", "charls_amd.h"), __file__]
-    device_newest, host_newest = newest(device_files + [__file__]), newest(host_deps)
-    flags_given = bool(os.environ.get("CHARLS_AMD_CXXFLAGS", "").split())
+        [public_header, __file__]
+    device_newest, host_newest = newest(device_deps), newest(host_deps)
     for src in SOURCES:
         obj = os.path.join(obj_dir, src.replace("/", "_") + ".o")
         objs.append(obj)
         stale_after = device_newest if src.startswith("device/") else host_newest
-        if not flags_given and os.path.exists(obj) and os.path.getmtime(obj) >= stale_after:
+        if not force and os.path.exists(obj) and os.path.getmtime(obj) >= stale_after and _read_stamp(_stamp_of(obj)) == stamp:
             continue
+        if os.path.exists(_stamp_of(obj)):
+            os.remove(_stamp_of(obj))  # (written again when the object is: a compile that fails leaves no stamp behind)
         cmd = [HIPCC, *common, "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd))
-        procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+        procs.append((src, obj, _start_compile(cmd)))
+    if os.path.exists(_stamp_of(OUT)):
+        os.remove(_stamp_of(OUT))
     failed = False
-    for src, p in procs:
+    for src, obj, p in procs:
         out, _ = p.communicate()
         if p.returncode != 0:
             failed = True
             sys.stderr.write(f"--- {src}\n{out.decode()}\n")
-        elif verbose and out:
-            sys.stderr.write(out.decode())
+        else:
+            _write_stamp(_stamp_of(obj), stamp)
+            if verbose and out:
+                sys.stderr.write(out.decode())
     if failed:
         raise RuntimeError("hipcc failed")
     # The scratch check needs llvm-objcopy / clang-offload-bundler / llvm-readelf of the ROCm LLVM (ROCM_LLVM_BIN).  A kernel with a
@@ -159,7 +199,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     for out, soname in ((OUT, "libcharls_amd.so"), (OUT_ALIAS, "libcharls.so.3")):
         link = [HIPCC, "--offload-arch=" + OFFLOAD_ARCH, "-shared", "-fPIC", *objs, "-o", out, "-Wl,-soname," + soname,
                 "-Wl,--no-undefined", "-Wl,--version-script=" + VERSION_SCRIPT, "-ldl"]
-        subprocess.check_call(link)
+        _link(link)
+    _write_stamp(_stamp_of(OUT), stamp)
     dev_link = os.path.join(OUT_DIR, "libcharls.so")  # what -lcharls resolves at link time
     if os.path.lexists(dev_link):
         os.remove(dev_link)

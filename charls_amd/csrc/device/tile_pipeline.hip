@@ -295,6 +295,50 @@ JLS_DEV void block_exclusive_scan(uint32_t& lo, uint32_t& hi, uint32_t* s_tmp)
     }
 }
 
+// The same for two independent series at once (a[] and b[], `count` values each, held like lo / hi above): both go through
+// the same shuffle passes and the same pair of barriers, and the second half is skipped when every value has a thread of
+// its own (count <= blockDim.x: the 367 chains on 512 threads -- two barriers where two calls of the function above take
+// eight).  s_tmp: two words per wavefront (16 words).  All threads of the workgroup call it; count is uniform.
+JLS_DEV void block_exclusive_scan_pair(uint32_t (&a)[2], uint32_t (&b)[2], uint32_t count, uint32_t* s_tmp)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (int)(blockDim.x >> 6);
+    const int halves = count > blockDim.x ? 2 : 1;
+    uint32_t carry_a = 0, carry_b = 0;
+    for (int half = 0; half < halves; ++half)
+    {
+        uint32_t incl_a = a[half], incl_b = b[half];
+        for (int delta = 1; delta < 64; delta <<= 1)
+        {
+            const uint32_t up_a = __shfl_up(incl_a, delta), up_b = __shfl_up(incl_b, delta);
+            if (lane >= delta)
+            {
+                incl_a += up_a;
+                incl_b += up_b;
+            }
+        }
+        __syncthreads(); // s_tmp free again
+        if (lane == 63)
+        {
+            s_tmp[wave] = incl_a;
+            s_tmp[kWaves + wave] = incl_b;
+        }
+        __syncthreads();
+        uint32_t before_a = carry_a, before_b = carry_b, all_a = 0, all_b = 0;
+        for (int w2 = 0; w2 < waves; ++w2)
+        {
+            const uint32_t na = s_tmp[w2], nb = s_tmp[kWaves + w2];
+            before_a += w2 < wave ? na : 0;
+            before_b += w2 < wave ? nb : 0;
+            all_a += na;
+            all_b += nb;
+        }
+        a[half] = before_a + incl_a - a[half];
+        b[half] = before_b + incl_b - b[half];
+        carry_a += all_a;
+        carry_b += all_b;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // The lines of a tile and the line above it, staged in LDS (planar scans): analysis reads every sample five times (x, Ra,
 // Rb, Rc, Rd); out of LDS those reads cost an LDS latency instead of a trip to the L2, and the staging itself is wide
@@ -757,68 +801,68 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
     JLS_PHASE(2);
     __syncthreads();
     JLS_PHASE(3);
-    // ---- offsets: chains in order, inside a chain the segments in (raster) order; per line, the number of samples
-    // inside runs from the first sample of every chunk on
+    // ---- per line, the number of samples inside runs from the first sample of every chunk on: 64 for every chunk of the
+    // unbroken row of all-ones masks that starts with the chunk, plus the trailing ones of the mask behind that row (0 behind
+    // the line's last chunk).  A line to a wavefront, a chunk to a lane (64 chunks at a time, from the end of the line: a
+    // line has at most kMaxTileSamples / 64 = 128): one ballot of "all ones" and one shuffle give every entry, where one
+    // thread per line walked the chunks backwards through LDS behind the scans below, the other wavefronts at the barrier.
+    // (The masks are final at the barrier above; the table is read in P2.)
+    for (uint32_t r = (uint32_t)wave; r < g.tile_lines; r += kWaves)
     {
-        uint32_t n[2] = {0, 0};
-        for (int half = 0; half < 2; ++half)
+        uint32_t behind = 0; // lead of the first chunk behind these 64
+        for (uint32_t k0 = (chunks - 1) / 64 * 64;; k0 -= 64)
         {
-            const uint32_t c = threadIdx.x + (uint32_t)half * kThreads;
-            if (c < (uint32_t)kChains)
-                for (uint32_t sgm = 0; sgm < g.segments; ++sgm)
-                    n[half] += s_segoff[sgm * kChains + c];
+            const uint32_t k = k0 + (uint32_t)lane;
+            const unsigned long long m = k < chunks ? s_noev[r * chunks + k] : 0ull;
+            const bool full = m == ~0ull;
+            const uint32_t own = full ? 64u : (uint32_t)__ffsll(~m) - 1;
+            const unsigned long long rest = __ballot(full) >> lane; // bit j: chunk k + j is all ones
+            const uint32_t ones = rest == ~0ull ? 64u : (uint32_t)__ffsll(~rest) - 1; // (<= 64 - lane)
+            const uint32_t next = __shfl(own, (int)((lane + ones) & 63u));
+            const uint32_t lead = 64u * ones + ((uint32_t)lane + ones < 64u ? next : behind);
+            if (k < chunks)
+                s_lead[r * (chunks + 1) + k] = lead;
+            behind = __shfl(lead, 0);
+            if (k0 == 0)
+                break;
         }
-        uint32_t off[2] = {n[0], n[1]};
-        block_exclusive_scan(off[0], off[1], s_tmp);
-        for (int half = 0; half < 2; ++half)
-        {
-            const uint32_t c = threadIdx.x + (uint32_t)half * kThreads;
-            if (c < (uint32_t)kChains)
-            {
-                s_tileoff[c] = off[half];
-                s_count[c] = n[half];
-                s_global[c] = w.seg[(size_t)tile * kChains + c];
-                uint32_t running = off[half];
-                for (uint32_t sgm = 0; sgm < g.segments; ++sgm)
-                {
-                    const uint32_t m = s_segoff[sgm * kChains + c];
-                    s_segoff[sgm * kChains + c] = running;
-                    running += m;
-                }
-            }
-        }
+        if (lane == 0)
+            s_lead[r * (chunks + 1) + chunks] = 0;
+    }
+    // ---- offsets: chains in order, inside a chain the segments in (raster) order.  A chain to a thread (kChains <=
+    // kThreads), which walks the chain's segment counters twice: to sum them, and to turn them into running offsets.  (Round
+    // 10 also tried the counters of all kSegments segments in registers, one unrolled, predicated batch in and one out: 26
+    // VGPRs more and the kernel 0.8 ms per pass of 512 frames SLOWER -- the bench's tiles have eight segments; not kept.)
+    {
+        static_assert(kChains <= kThreads, "a chain per thread");
+        const uint32_t c = threadIdx.x;
+        const bool chain = c < (uint32_t)kChains;
+        uint32_t n = 0;
+        if (chain)
+            for (uint32_t sgm = 0; sgm < g.segments; ++sgm)
+                n += s_segoff[sgm * kChains + c];
         // the pieces cut into rows of 64 records for the way out (P3): row q belongs to chain s_rowchain[q]; the interruption
         // chain has no records
-        uint32_t rows[2], row_base[2];
-        for (int half = 0; half < 2; ++half)
+        const uint32_t rows = chain && c != (uint32_t)kInterruptChain ? (n + 63) / 64 : 0u;
+        uint32_t off[2] = {n, 0}, row_base[2] = {rows, 0};
+        block_exclusive_scan_pair(off, row_base, kChains, s_tmp);
+        if (chain)
         {
-            const uint32_t c = threadIdx.x + (uint32_t)half * kThreads;
-            rows[half] = row_base[half] = c < (uint32_t)kChains && c != (uint32_t)kInterruptChain ? (n[half] + 63) / 64 : 0u;
-        }
-        block_exclusive_scan(row_base[0], row_base[1], s_tmp);
-        for (int half = 0; half < 2; ++half)
-        {
-            const uint32_t c = threadIdx.x + (uint32_t)half * kThreads;
-            if (c < (uint32_t)kChains)
+            s_tileoff[c] = off[0];
+            s_count[c] = n;
+            s_global[c] = w.seg[(size_t)tile * kChains + c];
+            uint32_t running = off[0];
+            for (uint32_t sgm = 0; sgm < g.segments; ++sgm)
             {
-                s_rowbase[c] = row_base[half];
-                for (uint32_t j = 0; j < rows[half]; ++j)
-                    s_rowchain[row_base[half] + j] = (uint16_t)c;
-                if (c == (uint32_t)kChains - 1)
-                    s_rowbase[kChains] = row_base[half] + rows[half];
+                const uint32_t m = s_segoff[sgm * kChains + c];
+                s_segoff[sgm * kChains + c] = running;
+                running += m;
             }
-        }
-        if (threadIdx.x >= kThreads - g.tile_lines)
-        { // (the last threads: they have no chain of their own to scan)
-            const uint32_t r = kThreads - 1 - threadIdx.x;
-            uint32_t lead = 0;
-            s_lead[r * (chunks + 1) + chunks] = 0;
-            for (uint32_t k = chunks; k-- > 0;)
-            {
-                const unsigned long long m = s_noev[r * chunks + k];
-                lead = m == ~0ull ? 64 + lead : (uint32_t)__ffsll(~m) - 1;
-                s_lead[r * (chunks + 1) + k] = lead;
-            }
+            s_rowbase[c] = row_base[0];
+            for (uint32_t j = 0; j < rows; ++j)
+                s_rowchain[row_base[0] + j] = (uint16_t)c;
+            if (c == (uint32_t)kChains - 1)
+                s_rowbase[kChains] = row_base[0] + rows;
         }
     }
     JLS_PHASE(4);
@@ -1889,6 +1933,16 @@ JLS_DEV void expand_code(uint32_t word, uint64_t& bits, int& len)
     }
 }
 
+// Word i of a tile's part of the raw stream (pack_tiles): the tile's bits lie in `bits` from bit 0 of word 0 (MSB first; zeros
+// behind them), the stream has `head` (< 32) bits of the tiles before it in the tile's first word -- `carry`: those bits,
+// at the top of a word, zeros below.
+JLS_DEV uint32_t shifted_word(const uint32_t* bits, uint32_t i, uint32_t head, uint32_t carry)
+{
+    if (head == 0)
+        return bits[i];
+    return (i == 0 ? carry : bits[i - 1] << (32u - head)) | (bits[i] >> head);
+}
+
 struct __attribute__((packed)) UnalignedQuadPair
 {
     uint64_t lo, hi;
@@ -1948,8 +2002,10 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
             mine[q] = make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
         }
     }
-    { // the tile's pieces, chain by chain, in the order sort_tiles laid them out
-        uint32_t n[2] = {0, 0}, g[2] = {0, 0};
+    { // the tile's pieces, chain by chain, in the order sort_tiles laid them out, and their rows: the pieces are cut into rows
+      // of 64 code words for the way into LDS; row q belongs to chain s_rowchain[q].  (One scan for both, see
+      // block_exclusive_scan_pair: a workgroup of fewer than kChains threads holds two chains per thread.)
+        uint32_t n[2] = {0, 0}, g[2] = {0, 0}, rows[2] = {0, 0};
         for (int half = 0; half < 2; ++half)
         {
             const uint32_t c = threadIdx.x + (uint32_t)half * threads;
@@ -1957,10 +2013,11 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
             {
                 g[half] = w.seg[(size_t)tile * kChains + c];
                 n[half] = w.seg[(size_t)(tile + 1) * kChains + c] - g[half];
+                rows[half] = (n[half] + 63) / 64;
             }
         }
-        uint32_t off[2] = {n[0], n[1]};
-        block_exclusive_scan(off[0], off[1], s_tmp);
+        uint32_t off[2] = {n[0], n[1]}, row_base[2] = {rows[0], rows[1]};
+        block_exclusive_scan_pair(off, row_base, kChains, s_tmp);
         for (int half = 0; half < 2; ++half)
         {
             const uint32_t c = threadIdx.x + (uint32_t)half * threads;
@@ -1969,28 +2026,6 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
                 s_tileoff[c] = off[half];
                 s_count[c] = n[half];
                 s_global[c] = g[half];
-            }
-        }
-    }
-    JLS_PHASE(9);
-    __syncthreads();
-    JLS_PHASE(10);
-    { // ---- the tile's code words into LDS.  The pieces are cut into rows of 64 words; row q belongs to chain s_rowchain[q].
-      // A wavefront takes sixteen rows at a time and requests them together: fetched piece by piece (a piece is ~80 events on
-      // average, a few are hundreds), it spent its time waiting for one trip to memory per row.
-        uint32_t rows[2] = {0, 0};
-        for (int half = 0; half < 2; ++half)
-        {
-            const uint32_t c = threadIdx.x + (uint32_t)half * threads;
-            rows[half] = c < (uint32_t)kChains ? (s_count[c] + 63) / 64 : 0u;
-        }
-        uint32_t row_base[2] = {rows[0], rows[1]};
-        block_exclusive_scan(row_base[0], row_base[1], s_tmp);
-        for (int half = 0; half < 2; ++half)
-        {
-            const uint32_t c = threadIdx.x + (uint32_t)half * threads;
-            if (c < (uint32_t)kChains)
-            {
                 s_rowbase[c] = row_base[half];
                 for (uint32_t j = 0; j < rows[half]; ++j)
                     s_rowchain[row_base[half] + j] = (uint16_t)c;
@@ -1998,8 +2033,13 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
                     s_rowbase[kChains] = row_base[half] + rows[half];
             }
         }
-        __syncthreads();
-        JLS_PHASE(11);
+    }
+    JLS_PHASE(9);
+    __syncthreads();
+    JLS_PHASE(11);
+    { // ---- the tile's code words into LDS.  A wavefront takes sixteen rows at a time and requests them together: fetched
+      // piece by piece (a piece is ~80 events on average, a few are hundreds), it spent its time waiting for one trip to
+      // memory per row.
         const uint32_t total_rows = s_rowbase[kChains];
         constexpr int kRows = 16; // rows a wavefront requests together
         for (uint32_t q0 = (uint32_t)wave * kRows; q0 < total_rows; q0 += kPackWaves * kRows)
@@ -2077,65 +2117,26 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
         __syncthreads();
     }
     JLS_PHASE(15);
-    // ---- where this tile starts: the first wavefront looks back, 64 predecessors at a time (see write_raw_bits)
-    if (threadIdx.x < 64)
-    {
-        const uint64_t own = s_scan[threads - 1];
-        const uint32_t b = tile;
-        if (lane == 0)
-            store_relaxed(&w.blockbase[b], (b == 0 ? pipe::kBlockUpTo : pipe::kBlockOwn) | own);
-        uint64_t start = 0;
-        uint32_t reach = b; // tiles [reach, b) are accounted for in `start`
-        while (reach > 0)
-        {
-            const bool in_window = (uint32_t)lane < reach;
-            const uint32_t j = in_window ? reach - 1 - (uint32_t)lane : 0;
-            uint64_t state = 0;
-            do
-            {
-                state = in_window ? load_relaxed(&w.blockbase[j]) : pipe::kBlockOwn;
-            } while (__any((state >> 62) == 0));
-            const unsigned long long knows = __ballot(in_window && (state >> 62) == 2);
-            const int last = knows ? (int)__ffsll(knows) - 1 : 63;
-            uint64_t part = in_window && lane <= last ? state & pipe::kBlockValue : 0;
-            for (int delta = 32; delta > 0; delta >>= 1)
-                part += __shfl_xor(part, delta);
-            start += part;
-            if (knows)
-                break;
-            reach = reach > 64 ? reach - 64 : 0;
-        }
-        if (lane == 0)
-        {
-            if (b != 0)
-                store_relaxed(&w.blockbase[b], pipe::kBlockUpTo | (start + own));
-            s_tmp[12] = (uint32_t)start; // (two words of the scan scratch: the kernel has no static LDS, its dynamic
-            s_tmp[13] = (uint32_t)(start >> 32); // region may then be as large as the CU's)
-            if (b + 1 == tiles)
-                *w.total_bits = start + own;
-        }
-    }
-    JLS_PHASE(16);
-    __syncthreads();
-    JLS_PHASE(17);
-    // ---- the tile's bits are put together in LDS and leave as whole
-    // words, coalesced.  Nothing of the raw stream is cleared beforehand and no word is written twice: the last, partial
-    // word of a tile is not stored by that tile but PUBLISHED (tile_tail: the bits and a valid flag in one 64-bit word, like
-    // the look-back states -- the word carries everything, no fence), and the next tile, whose first bits complete it, ORs
-    // it into its own first word before storing that.  A tile publishes as soon as its bits are in LDS and only then waits
-    // for its predecessor (the waits do not form a chain, except through tiles of less than a word).  (Round 2 cleared the
-    // whole buffer, 17.8 MB per frame for 7.3 MB of stream, and every thread wrote its two or three words with atomics:
-    // 48 MB of write traffic.)
-    const uint64_t tile_start = (uint64_t)s_tmp[12] | ((uint64_t)s_tmp[13] << 32);
+    // ---- The tile's bits are put together in LDS as if the tile started on a word boundary, and only then does the first
+    // wavefront look back for where it really starts: the tile's own bit count is published before the assembly (the
+    // order "publish, then wait" of the look-back is what it was), and by the time the assembly is done the tiles before
+    // this one -- started before it -- have long published theirs, so the look-back is one trip to memory instead of a wait
+    // with seven wavefronts at a barrier behind it.  The shift by the `head` bits of the stream's word that the tile before
+    // this one began is applied on the way out (shifted_word).
     const uint32_t tile_bits = s_scan[threads - 1];
-    const uint32_t head = (uint32_t)(tile_start & 31);
-    const uint32_t tile_words = (head + tile_bits + 31) / 32; // (<= pack_bits_words: a code has at most LIMIT bits per sample it stands for)
-    for (uint32_t i = threadIdx.x; i < tile_words + 1; i += threads)
+    if (threadIdx.x == 0)
+        store_relaxed(&w.blockbase[tile], (tile == 0 ? pipe::kBlockUpTo : pipe::kBlockOwn) | (uint64_t)tile_bits);
+    // s_bits holds pack_bits_words = tile_capacity * LIMIT / 32 + 2 words and a code has at most LIMIT bits per sample it stands
+    // for, so local_words + 1 <= pack_bits_words.  Words [0, local_words] are zeroed here; the assembly writes words [0,
+    // local_words), and shifted_word reads bits[tile_words - 1] at most, which is bits[local_words] at most (tile_words =
+    // (head + tile_bits + 31) / 32 <= local_words + 1): a zeroed word, never one beyond the buffer.
+    const uint32_t local_words = (tile_bits + 31) / 32;
+    for (uint32_t i = threadIdx.x; i < local_words + 1; i += threads)
         s_bits[i] = 0;
     __syncthreads();
     if (sum != 0)
     {
-        const uint32_t bitpos = head + s_scan[threadIdx.x] - sum;
+        const uint32_t bitpos = s_scan[threadIdx.x] - sum;
         uint32_t word_at = bitpos >> 5;
         const uint32_t first_word = word_at;
         uint32_t pending = bitpos & 31; // the leading bits of the first word belong to the previous thread
@@ -2180,37 +2181,86 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
     JLS_PHASE(18);
     __syncthreads();
     JLS_PHASE(19);
+    // ---- where this tile starts: the first wavefront looks back, 64 predecessors at a time (see write_raw_bits); its first
+    // thread then settles the words this tile shares with its neighbours.  Nothing of the raw stream is cleared beforehand
+    // and no word is written twice: the last, partial word of a tile is not stored by that tile but PUBLISHED (tile_tail:
+    // the bits and a valid flag in one 64-bit word, like the look-back states -- the word carries everything, no fence), and
+    // the next tile, whose first bits complete it, ORs it into its own first word before storing that.  A tile publishes
+    // before it waits for its predecessor (the waits do not form a chain, except through tiles of less than a word).
+    // (Round 2 cleared the whole buffer, 17.8 MB per frame for 7.3 MB of stream, and every thread wrote its two or three
+    // words with atomics: 48 MB of write traffic.)
     const bool last_tile = tile + 1 == tiles;
-    const bool shared_first = head != 0;                                     // my first word starts in the tile before
-    const bool partial_last = ((head + tile_bits) & 31u) != 0 && !last_tile; // my last word is completed by the next tile
     constexpr uint64_t kTailValid = 1ull << 63;
-    if (threadIdx.x == 0)
+    if (threadIdx.x < 64)
     {
-        // (with no word of its own -- tile_words 0, or one word that neither starts nor ends here -- a tile passes on what its
-        // predecessor left, plus its own bits)
-        const bool own_tail = tile_words >= 2 || !shared_first;
-        if (own_tail)
-            store_relaxed(&w.tile_tail[tile], kTailValid | (partial_last ? s_bits[tile_words - 1] : 0u));
-        if (shared_first)
-        { // (tile 0 starts at bit 0)
-            uint64_t before;
+        const uint64_t own = tile_bits;
+        const uint32_t b = tile;
+        uint64_t start = 0;
+        uint32_t reach = b; // tiles [reach, b) are accounted for in `start`
+        while (reach > 0)
+        {
+            const bool in_window = (uint32_t)lane < reach;
+            const uint32_t j = in_window ? reach - 1 - (uint32_t)lane : 0;
+            uint64_t state = 0;
             do
-                before = load_relaxed(&w.tile_tail[tile - 1]);
-            while ((before & kTailValid) == 0);
-            s_bits[0] |= (uint32_t)before;
+            {
+                state = in_window ? load_relaxed(&w.blockbase[j]) : pipe::kBlockOwn;
+            } while (__any((state >> 62) == 0));
+            const unsigned long long knows = __ballot(in_window && (state >> 62) == 2);
+            const int last = knows ? (int)__ffsll(knows) - 1 : 63;
+            uint64_t part = in_window && lane <= last ? state & pipe::kBlockValue : 0;
+            for (int delta = 32; delta > 0; delta >>= 1)
+                part += __shfl_xor(part, delta);
+            start += part;
+            if (knows)
+                break;
+            reach = reach > 64 ? reach - 64 : 0;
         }
-        if (!own_tail)
-            store_relaxed(&w.tile_tail[tile], kTailValid | (partial_last ? s_bits[0] : 0u));
+        if (lane == 0)
+        {
+            if (b != 0)
+                store_relaxed(&w.blockbase[b], pipe::kBlockUpTo | (start + own));
+            if (b + 1 == tiles)
+                *w.total_bits = start + own;
+            const uint32_t head = (uint32_t)(start & 31);
+            const uint32_t tile_words = (head + tile_bits + 31) / 32;
+            const bool shared_first = head != 0;                                     // my first word starts in the tile before
+            const bool partial_last = ((head + tile_bits) & 31u) != 0 && !last_tile; // my last word is completed by the next tile
+            // (with no word of its own -- tile_words 0, or one word that neither starts nor ends here -- a tile passes on what its
+            // predecessor left, plus its own bits)
+            const bool own_tail = tile_words >= 2 || !shared_first;
+            if (own_tail)
+                store_relaxed(&w.tile_tail[tile], kTailValid | (partial_last ? shifted_word(s_bits, tile_words - 1, head, 0u) : 0u));
+            uint32_t carry = 0; // the bits of my first word that the tile before me left
+            if (shared_first)
+            { // (tile 0 starts at bit 0)
+                uint64_t before;
+                do
+                    before = load_relaxed(&w.tile_tail[tile - 1]);
+                while ((before & kTailValid) == 0);
+                carry = (uint32_t)before;
+            }
+            if (!own_tail)
+                store_relaxed(&w.tile_tail[tile], kTailValid | (partial_last ? shifted_word(s_bits, 0, head, carry) : 0u));
+            s_tmp[12] = (uint32_t)start; // (three words of the scan scratch: the kernel has no static LDS, its dynamic
+            s_tmp[13] = (uint32_t)(start >> 32); // region may then be as large as the CU's)
+            s_tmp[14] = carry;
+        }
     }
+    JLS_PHASE(16);
     __syncthreads();
     JLS_PHASE(20);
+    const uint64_t tile_start = (uint64_t)s_tmp[12] | ((uint64_t)s_tmp[13] << 32);
+    const uint32_t head = (uint32_t)(tile_start & 31), carry = s_tmp[14];
+    const uint32_t tile_words = (head + tile_bits + 31) / 32; // (<= local_words + 1)
+    const bool partial_last = ((head + tile_bits) & 31u) != 0 && !last_tile;
     const uint64_t first_global = tile_start >> 5;
     const uint32_t stored_words = partial_last ? tile_words - 1 : tile_words;
     for (uint32_t i = threadIdx.x; i < stored_words; i += threads)
     {
         const uint64_t at = first_global + i;
         if (at < w.raw_words)
-            w.raw[at] = __builtin_bswap32(s_bits[i]);
+            w.raw[at] = __builtin_bswap32(shifted_word(s_bits, i, head, carry));
     }
     if (last_tile && threadIdx.x < 4)
     { // the stuffing stage reads a few bytes past the last bit: zeros

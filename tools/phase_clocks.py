@@ -17,10 +17,11 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {
     "sort_tiles": {0: "lines requested", 1: "tables zeroed + barrier (lines arrive)", 2: "P1 keys, histogram", 3: "barrier",
-                   4: "offsets", 5: "barrier", 6: "P2 ranks, records", 7: "barrier", 8: "P3 pieces out"},
-    "pack_tiles": {9: "slot map requested, piece table", 10: "barrier", 11: "row table + barrier", 12: "code words into LDS",
-                   13: "barrier", 14: "bits of the thread's samples", 15: "scan of the bit counts", 16: "look-back (wavefront 0)",
-                   17: "barrier (the others wait for the look-back)", 18: "bits into LDS", 19: "barrier", 20: "barrier + tails (thread 0)", 21: "words out"},
+                   4: "run leads, offsets", 5: "barrier", 6: "P2 ranks, records", 7: "barrier", 8: "P3 pieces out"},
+    # (in the order of the kernel: the bits go into LDS before the look-back)
+    "pack_tiles": {9: "slot map requested, piece and row tables", 11: "barrier", 12: "code words into LDS", 13: "barrier",
+                   14: "bits of the thread's samples", 15: "scan of the bit counts", 18: "bits into LDS", 19: "barrier",
+                   16: "look-back, shared words (wavefront 0)", 20: "barrier (the others wait for wavefront 0)", 21: "words out"},
 }
 
 
