@@ -29,6 +29,15 @@ class Gather(C.Structure):  # charls_amd_gather
                 ("offsets", C.POINTER(C.c_uint64)), ("total_bytes", C.POINTER(C.c_uint64)), ("transport", C.c_int32)]
 
 
+class FrameSource(C.Structure):  # charls_amd_frame_source
+    _fields_ = [("params", CodecParams), ("d_pixels", C.c_void_p), ("stride", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_stream_bytes", C.c_uint64)]
+
+
+class FrameDest(C.Structure):  # charls_amd_frame_dest
+    _fields_ = [("d_pixels", C.c_void_p), ("capacity_bytes", C.c_uint64), ("stride", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER_COPIES = 0, 1, 2
 
 
@@ -85,6 +94,14 @@ def _bind(lib):
     l.charls_amd_decode_batch_device_packed.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.c_void_p, C.c_size_t, C.c_uint32,
                                                         C.POINTER(CodecParams), i32p, C.c_void_p]
     l.charls_amd_decode_batch_device_packed.restype = C.c_int32
+    l.charls_amd_probe_batch_device_packed.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.POINTER(CodecParams), u64p, i32p, C.c_void_p]
+    l.charls_amd_probe_batch_device_packed.restype = C.c_int32
+    l.charls_amd_decode_batch_device_ragged.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.POINTER(FrameDest), C.POINTER(CodecParams),
+                                                        i32p, C.c_void_p]
+    l.charls_amd_decode_batch_device_ragged.restype = C.c_int32
+    l.charls_amd_encode_batch_device_ragged.argtypes = [C.c_uint32, C.POINTER(FrameSource), C.c_void_p, C.c_size_t, C.c_uint32, u64p, u64p,
+                                                        i32p, C.c_void_p]
+    l.charls_amd_encode_batch_device_ragged.restype = C.c_int32
     l._batch_bound = True
     return l
 
@@ -385,6 +402,116 @@ def decode_batch_packed(packed, offsets, sizes, out, *, stride=0, frame_pitch=No
     if rc != 0:
         raise capi.JpegLSError(rc, "charls_amd_decode_batch_device_packed")
     return p, errcs, last_timings(lib)
+
+
+# ---- ragged frames (charls_amd.h part 2e): a table entry per frame, tensors that need not share an allocation --------------
+
+def codec_params(width, height, bits_per_sample=8, component_count=1, interleave_mode=0, near_lossless=0, *, color_transformation=0,
+                 preset=(0, 0, 0, 0, 0), encoding_options=0, restart_interval=0) -> CodecParams:
+    return CodecParams(capi.FrameInfo(width, height, bits_per_sample, component_count), near_lossless, interleave_mode,
+                       color_transformation, capi.PcParameters(*preset), encoding_options, restart_interval)
+
+
+def _row_stride(t, planar):
+    """The `stride` argument for tensor t: 0 (minimal) for a contiguous one; for a view -- a tile cut out of an image -- the
+    bytes from row to row: (H, W) and (H, W, C) views with contiguous rows, (C, H, W) views whose planes follow each other."""
+    if t.is_contiguous():
+        return 0
+    if t.dim() == 3 and planar:
+        assert t.stride(2) == 1 and t.stride(0) == t.stride(1) * t.shape[1], "a planar view's planes must follow each other"
+        return t.stride(1) * t.element_size()
+    assert t.dim() in (2, 3) and t.stride(-1) == 1 and (t.dim() == 2 or t.stride(1) == t.shape[2]), "a view's rows must be contiguous"
+    return t.stride(0) * t.element_size()
+
+
+def probe_packed(packed, offsets, sizes, *, lib=None):
+    """charls_amd_probe_batch_device_packed: what the streams packed[offsets[f]:offsets[f] + sizes[f]] hold, without decoding
+    them.  Returns (params -- a ctypes array of CodecParams --, frame_bytes uint64, errcs); probe, then allocate, then decode."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert packed.is_cuda and packed.is_contiguous()
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    count = len(sizes)
+    assert len(offsets) >= count
+    params = (CodecParams * max(count, 1))()
+    frame_bytes = np.zeros(count, dtype=np.uint64)
+    errcs = np.zeros(count, dtype=np.int32)
+    stream = torch.cuda.current_stream(packed.device).cuda_stream
+    rc = l.charls_amd_probe_batch_device_packed(count, packed.data_ptr(), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                sizes.ctypes.data_as(C.POINTER(C.c_uint64)), params,
+                                                frame_bytes.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_probe_batch_device_packed")
+    return params, frame_bytes, errcs
+
+
+def decode_batch_ragged(packed, offsets, sizes, outs, *, strides=None, capacities=None, lib=None):
+    """charls_amd_decode_batch_device_ragged: frame f of the packed streams into outs[f], a device tensor of its own (any
+    allocation, any shape of enough bytes; a view with padded rows states them through its strides).  strides / capacities:
+    per-frame overrides (bytes).  Returns (params -- a ctypes array, one CodecParams per frame --, errcs, gpu_ms)."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert packed.is_cuda and packed.is_contiguous()
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    count = len(sizes)
+    assert len(offsets) >= count and len(outs) == count
+    dests = (FrameDest * max(count, 1))()
+    for f, t in enumerate(outs):
+        assert t.is_cuda
+        assert strides is not None or t.is_contiguous() or t.dim() == 2, "a 3-D view: say its row stride (planar or interleaved?)"
+        stride = strides[f] if strides is not None else _row_stride(t, False)
+        if capacities is not None:
+            capacity = int(capacities[f])
+        elif t.is_contiguous():
+            capacity = t.numel() * t.element_size()
+        else:  # the view's extent: to the end of its last row
+            capacity = (sum((n - 1) * s for n, s in zip(t.shape, t.stride())) + 1) * t.element_size()
+        dests[f] = FrameDest(t.data_ptr(), capacity, int(stride), 0)
+    params = (CodecParams * max(count, 1))()
+    errcs = np.zeros(count, dtype=np.int32)
+    stream = torch.cuda.current_stream(packed.device).cuda_stream
+    rc = l.charls_amd_decode_batch_device_ragged(count, packed.data_ptr(), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 sizes.ctypes.data_as(C.POINTER(C.c_uint64)), dests, params,
+                                                 errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_decode_batch_device_ragged")
+    return params, errcs, last_timings(lib)
+
+
+def encode_batch_ragged(frames, params, packed, *, alignment=1, strides=None, max_stream_bytes=None, capacity=None, lib=None) -> PackedBatch:
+    """charls_amd_encode_batch_device_ragged: frames[f] -- a device tensor of its own: any allocation, the same tensor more
+    than once, a view into a larger image (a tile: its row stride is read from the view) -- coded with params[f] (CodecParams,
+    see codec_params; one CodecParams serves every frame).  The streams go back to back into `packed` in this order.  strides
+    / max_stream_bytes: per-frame overrides (bytes; 0 = minimal / part 1's estimate)."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert packed.is_cuda and packed.is_contiguous()
+    count = len(frames)
+    if isinstance(params, CodecParams):
+        params = [params] * count
+    assert len(params) == count
+    sources = (FrameSource * max(count, 1))()
+    for f, t in enumerate(frames):
+        assert t.is_cuda
+        stride = strides[f] if strides is not None else _row_stride(t, params[f].interleave_mode == 0)
+        sources[f] = FrameSource(params[f], t.data_ptr(), int(stride), 0, int(max_stream_bytes[f]) if max_stream_bytes is not None else 0)
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    sizes = np.zeros(count, dtype=np.uint64)
+    errcs = np.zeros(count, dtype=np.int32)
+    stream = torch.cuda.current_stream(packed.device).cuda_stream
+    rc = l.charls_amd_encode_batch_device_ragged(count, sources, packed.data_ptr(), packed.numel() if capacity is None else int(capacity),
+                                                 alignment, offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 sizes.ctypes.data_as(C.POINTER(C.c_uint64)), errcs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_encode_batch_device_ragged")
+    return PackedBatch(packed, offsets, sizes, errcs)
 
 
 def set_workspace_limit(nbytes: int, lib=None):

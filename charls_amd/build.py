@@ -37,6 +37,7 @@ SOURCES = [
     "host/batch_api.cpp",
     "host/batch_index.cpp",
     "host/batch_packed.cpp",
+    "host/batch_ragged.cpp",
     "host/multi_device.cpp",
 ]
 

@@ -96,6 +96,8 @@ void validate_encode(const charls_amd_codec_params& p, size_t frame_pitch, uint3
         raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_JPEGLS_PC_PARAMETERS);
     if (p.color_transformation != 0 && !color_transformation_possible(f, p.near_lossless, p.interleave_mode))
         raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_COLOR_TRANSFORMATION);
+    if (f.component_count * 3 + 32 > 400)
+        raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_COMPONENT_COUNT); // batch API: at most ~120 components (the prologue buffer)
     *stride_out = stride;
 }
 
@@ -122,22 +124,21 @@ thread_local bool t_force_rounds = false; // the batch encoder codes the compone
 
 } // namespace
 
-extern "C" charls_jpegls_errc charls_amd_encode_batch_device(const charls_amd_codec_params* params, uint32_t frame_count,
-                                                             const void* d_frames, size_t frame_pitch_bytes,
-                                                             uint32_t stride_arg, void* d_streams,
-                                                             size_t stream_pitch_bytes, uint64_t* sizes,
-                                                             charls_jpegls_errc* errcs, void* hip_stream)
-try
+void jls::check_encode_params(const charls_amd_codec_params& params, size_t frame_bytes, uint32_t stride_arg)
 {
-    check_pointer(params);
-    check_pointer(sizes);
-    check_pointer(errcs);
-    if (frame_count == 0)
-        return CHARLS_JPEGLS_ERRC_SUCCESS;
-    check_pointer(d_frames);
-    check_pointer(d_streams);
+    size_t stride = 0;
+    charls_jpegls_pc_parameters pc{};
+    validate_encode(params, frame_bytes, stride_arg, &stride, &pc);
+}
+
+// The batch encoder behind charls_amd_encode_batch_device (frames[i] = d_frames + i * frame_pitch_bytes) and
+// charls_amd_encode_batch_device_ragged (batch_ragged.cpp: the frames of one group of a window, wherever they lie): frame
+// i's pixels start at frames[i].  frame_count >= 1, the pointers are checked by the entry points.
+void jls::encode_batch_frames(const charls_amd_codec_params& p, uint32_t frame_count, const uint8_t* const* frames,
+                              size_t frame_pitch_bytes, uint32_t stride_arg, void* d_streams, size_t stream_pitch_bytes,
+                              uint64_t* sizes, charls_jpegls_errc* errcs, void* hip_stream)
+{
     dev::require_device();
-    const charls_amd_codec_params& p = *params;
     size_t stride = 0;
     charls_jpegls_pc_parameters pc{};
     validate_encode(p, frame_pitch_bytes, stride_arg, &stride, &pc);
@@ -156,8 +157,6 @@ try
     }
     if (p.color_transformation != 0)
         w.color_transform(p.color_transformation);
-    if (f.component_count * 3 + 32 > 400)
-        raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_COMPONENT_COUNT); // batch API: at most ~120 components
     if (w.start_of_frame(f))
         w.oversize_dimensions(f.height, f.width);
     if (!pc_is_default(p.preset_coding_parameters, default_pc(bit_max_value(f.bits_per_sample), p.near_lossless)) ||
@@ -209,7 +208,6 @@ try
 
     std::vector<ScanDesc> descs(frame_count);
     auto* slots = static_cast<uint8_t*>(d_streams);
-    const auto* frames = static_cast<const uint8_t*>(d_frames);
 
     EventTimer total(stream), scans(stream);
     double scan_ms = 0;
@@ -264,7 +262,7 @@ try
                 for (uint32_t r = 0; r < rounds; ++r)
                 {
                     ScanDesc d = base_desc(f, 1, 0, p.near_lossless, p.color_transformation, pc, 0);
-                    d.pixels = const_cast<uint8_t*>(frames) + (first + i) * frame_pitch_bytes + r * stride * f.height;
+                    d.pixels = const_cast<uint8_t*>(frames[first + i]) + r * stride * f.height;
                     d.pixel_stride = stride;
                     d.stream = priv + (static_cast<size_t>(i) * rounds + r) * capacity;
                     d.stream_capacity = std::min(stream_pitch_bytes, worst);
@@ -299,7 +297,7 @@ try
         {
             ScanDesc d = base_desc(f, comps_per_scan, p.interleave_mode, p.near_lossless, p.color_transformation, pc,
                                    p.restart_interval);
-            d.pixels = const_cast<uint8_t*>(frames) + i * frame_pitch_bytes + (p.interleave_mode == 0 ? r * stride * f.height : 0);
+            d.pixels = const_cast<uint8_t*>(frames[i]) + (p.interleave_mode == 0 ? r * stride * f.height : 0);
             d.pixel_stride = stride;
             d.line_scratch = d_scratch.as<uint16_t>() + i * scratch_samples;
             descs[i] = d;
@@ -354,14 +352,34 @@ try
             ForceRounds() { t_force_rounds = true; }
             ~ForceRounds() { t_force_rounds = false; }
         } force;
-        const charls_jpegls_errc rc = charls_amd_encode_batch_device(params, last - i, frames + i * frame_pitch_bytes, frame_pitch_bytes, stride_arg,
-                                                                     slots + i * stream_pitch_bytes, stream_pitch_bytes, sizes + i, errcs + i, hip_stream);
-        if (rc != CHARLS_JPEGLS_ERRC_SUCCESS)
-            return rc;
+        encode_batch_frames(p, last - i, frames + i, frame_pitch_bytes, stride_arg, slots + i * stream_pitch_bytes, stream_pitch_bytes,
+                            sizes + i, errcs + i, hip_stream);
         i = last;
     }
     if (!redo_frames.empty())
         dev::last_timings() = kept;
+}
+
+extern "C" charls_jpegls_errc charls_amd_encode_batch_device(const charls_amd_codec_params* params, uint32_t frame_count,
+                                                             const void* d_frames, size_t frame_pitch_bytes,
+                                                             uint32_t stride_arg, void* d_streams,
+                                                             size_t stream_pitch_bytes, uint64_t* sizes,
+                                                             charls_jpegls_errc* errcs, void* hip_stream)
+try
+{
+    check_pointer(params);
+    check_pointer(sizes);
+    check_pointer(errcs);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    check_pointer(d_frames);
+    check_pointer(d_streams);
+    dev::require_device();
+    std::vector<const uint8_t*> frames(frame_count);
+    for (uint32_t i = 0; i < frame_count; ++i)
+        frames[i] = static_cast<const uint8_t*>(d_frames) + i * frame_pitch_bytes;
+    encode_batch_frames(*params, frame_count, frames.data(), frame_pitch_bytes, stride_arg, d_streams, stream_pitch_bytes, sizes, errcs,
+                        hip_stream);
     return CHARLS_JPEGLS_ERRC_SUCCESS;
 }
 catch (...)
@@ -369,17 +387,29 @@ catch (...)
     return current_exception_to_errc();
 }
 
-// The batch decoder behind charls_amd_decode_batch_device (slots: stream_at[i] = i * pitch) and
-// charls_amd_decode_batch_device_packed (batch_packed.cpp: stream_at = the caller's offset table): frame i's stream is the
-// sizes[i] bytes at d_streams + stream_at[i].  frame_count >= 1, the pointers are checked by the entry points.
+// The frames of the slot calls as a table of destinations: what the decoder below takes.
 void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, const uint64_t* stream_at, const uint64_t* sizes,
                                void* d_frames, size_t frame_pitch_bytes, uint32_t stride_arg,
                                charls_amd_codec_params* params_out, charls_jpegls_errc* errcs, void* hip_stream)
 {
+    std::vector<charls_amd_frame_dest> dests(frame_count);
+    for (uint32_t i = 0; i < frame_count; ++i)
+        dests[i] = charls_amd_frame_dest{static_cast<uint8_t*>(d_frames) + i * frame_pitch_bytes, frame_pitch_bytes, stride_arg, 0};
+    decode_batch_streams(frame_count, d_streams, stream_at, sizes, BatchDests{dests.data(), false, nullptr}, params_out, errcs, hip_stream);
+}
+
+// The batch decoder behind charls_amd_decode_batch_device (slots: stream_at[i] = i * pitch),
+// charls_amd_decode_batch_device_packed (batch_packed.cpp: stream_at = the caller's offset table) and the calls of part 2e
+// (batch_ragged.cpp: a destination per frame, or none -- the probe): frame i's stream is the sizes[i] bytes at
+// d_streams + stream_at[i] and goes to to.dests[i].  frame_count >= 1, the pointers are checked by the entry points.
+void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, const uint64_t* stream_at, const uint64_t* sizes,
+                               const BatchDests& to, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs,
+                               void* hip_stream)
+{
     dev::require_device();
     auto stream = static_cast<hipStream_t>(hip_stream);
     const auto* slots = static_cast<const uint8_t*>(d_streams);
-    auto* frames = static_cast<uint8_t*>(d_frames);
+    const bool probing = to.dests == nullptr;
 
     // Every frame's marker segments are parsed on the host by the part-1 reader.  Only a window of each stream is
     // fetched: the first `kWindow` bytes up front, later windows at the position each scan ended.
@@ -478,10 +508,62 @@ void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, cons
         parse(fr, i, [&](Frame& x) {
             x.reader.set_source(x.window.data(), x.window.size());
             x.reader.read_header();
-            if (x.reader.end_of_image())
+            if (x.reader.end_of_image() && !probing)
                 raise(CHARLS_JPEGLS_ERRC_INVALID_OPERATION); // abbreviated table stream: nothing to decode
             x.cursor = x.window_base + static_cast<size_t>(x.reader.position() - x.window.data());
         });
+
+    // What params_out says about a frame whose reader stands behind the header of its first scan.
+    auto params_of = [](const StreamReader& r) {
+        return charls_amd_codec_params{r.frame_info(), r.parameters().near_lossless, r.scan_interleave_mode(), r.parameters().transformation,
+                                       r.preset_coding_parameters(), 0, r.parameters().restart_interval};
+    };
+    if (probing)
+    {
+        // part 1's get_destination_size(stride 0) (decoder_api.cpp: destination_size) beside the parameters; an abbreviated
+        // table stream has no frame: read_header succeeds on it, and it reports zeros
+        for (uint32_t i = 0; i < frame_count; ++i)
+        {
+            Frame& x = fr[i];
+            params_out[i] = charls_amd_codec_params{};
+            to.frame_bytes_out[i] = 0;
+            if (x.errc == CHARLS_JPEGLS_ERRC_SUCCESS && !x.reader.end_of_image())
+                try
+                {
+                    const charls_frame_info& f = x.reader.frame_info();
+                    to.frame_bytes_out[i] = checked_mul(checked_mul(checked_mul(static_cast<size_t>(f.component_count), f.height), f.width),
+                                                        bytes_per_sample(f.bits_per_sample));
+                    params_out[i] = params_of(x.reader);
+                }
+                catch (const error& e)
+                {
+                    x.errc = e.code;
+                }
+            errcs[i] = x.errc;
+        }
+        dev::Timings& t = dev::last_timings(); // (no kernel of the decoder ran)
+        t.values[0] = t.values[1] = 0;
+        t.count = 2;
+        return;
+    }
+    // A destination per frame of the caller's own: stride and capacity against the whole frame -- the rows of all planes of a
+    // planar frame --, before any of its scans is decoded.
+    for (uint32_t i = 0; i < frame_count && to.ragged; ++i)
+    {
+        Frame& x = fr[i];
+        if (x.done)
+            continue;
+        const charls_frame_info& f = x.reader.frame_info();
+        const int32_t ilv = x.reader.scan_interleave_mode();
+        const size_t row = (ilv == 0 ? 1u : x.reader.scan_component_count()) * static_cast<size_t>(f.width) * bytes_per_sample(f.bits_per_sample);
+        const size_t rows = static_cast<size_t>(f.height) * (ilv == 0 ? x.reader.component_count() : 1u);
+        const size_t stride = to.dests[i].stride == 0 ? row : to.dests[i].stride;
+        if (stride < row)
+            x.errc = CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_STRIDE;
+        else if (to.dests[i].capacity_bytes < stride * rows - (stride - row))
+            x.errc = CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE;
+        x.done = x.errc != CHARLS_JPEGLS_ERRC_SUCCESS;
+    }
 
     dev::DeviceBuffer d_descs, d_results, d_scratch;
     std::vector<ScanDesc> descs;
@@ -498,18 +580,18 @@ void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, cons
         const int32_t ilv = x.reader.scan_interleave_mode();
         const uint32_t nc = x.reader.scan_component_count();
         const size_t row = (ilv == 0 ? 1u : nc) * static_cast<size_t>(f.width) * bytes_per_sample(f.bits_per_sample);
-        size_t stride = stride_arg;
+        size_t stride = to.dests[i].stride;
         if (stride == 0)
             stride = row;
         else if (stride < row)
             raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_STRIDE);
         const size_t need = (ilv == 0 ? stride * nc * f.height : stride * f.height) - (stride - row);
-        if (frame_pitch_bytes < x.plane_offset + need)
+        if (to.dests[i].capacity_bytes < x.plane_offset + need)
             raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
         ScanDesc d = base_desc(f, static_cast<int32_t>(nc), ilv, x.reader.parameters().near_lossless,
                                x.reader.parameters().transformation, x.reader.validated_pc(),
                                x.reader.parameters().restart_interval);
-        d.pixels = frames + i * frame_pitch_bytes + x.plane_offset;
+        d.pixels = static_cast<uint8_t*>(to.dests[i].d_pixels) + x.plane_offset;
         d.pixel_stride = stride;
         d.stream = const_cast<uint8_t*>(slots) + stream_at[i] + x.cursor;
         d.stream_capacity = sizes[i] - x.cursor;
@@ -519,11 +601,11 @@ void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, cons
         return d;
     };
     auto report_params = [&](Frame& x, uint32_t index) {
-        if (params_out && index < params_from)
+        if (params_out && to.ragged)
+            params_out[index] = params_of(x.reader);
+        else if (params_out && index < params_from)
         {
-            *params_out = charls_amd_codec_params{x.reader.frame_info(), x.reader.parameters().near_lossless,
-                                                  x.reader.scan_interleave_mode(), x.reader.parameters().transformation,
-                                                  x.reader.preset_coding_parameters(), 0, x.reader.parameters().restart_interval};
+            *params_out = params_of(x.reader);
             params_from = index;
         }
     };
@@ -604,8 +686,8 @@ void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, cons
             { // every plane must fit behind the first (the rounds raise the error where it belongs otherwise)
                 const charls_frame_info& f = x.reader.frame_info();
                 const size_t row = static_cast<size_t>(f.width) * bytes_per_sample(f.bits_per_sample);
-                const size_t stride = stride_arg == 0 ? row : stride_arg;
-                if (stride < row || frame_pitch_bytes < checked_mul(checked_mul(stride, f.height), x.reader.component_count()) - (stride - row))
+                const size_t stride = to.dests[i].stride == 0 ? row : to.dests[i].stride;
+                if (stride < row || to.dests[i].capacity_bytes < checked_mul(checked_mul(stride, f.height), x.reader.component_count()) - (stride - row))
                     continue;
                 p.scans.push_back(scan_desc(i, probe[i], scratch_total));
             }
@@ -663,7 +745,7 @@ void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, cons
                 Frame& y = probe[p.frame];
                 const charls_frame_info f = y.reader.frame_info();
                 const size_t row = static_cast<size_t>(f.width) * bytes_per_sample(f.bits_per_sample);
-                y.plane_offset += (stride_arg ? stride_arg : row) * f.height;
+                y.plane_offset += (to.dests[p.frame].stride ? to.dests[p.frame].stride : row) * f.height;
                 parse(probe, p.frame, [&](Frame& z) {
                     z.reader.continue_on_window(z.window.data(), z.window.size());
                     z.reader.read_next_start_of_scan();
@@ -809,7 +891,7 @@ void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, cons
             if (!last)
             {
                 const size_t row = (ilv == 0 ? 1u : nc) * static_cast<size_t>(f.width) * bytes_per_sample(f.bits_per_sample);
-                const size_t stride = stride_arg ? stride_arg : row;
+                const size_t stride = to.dests[i].stride ? to.dests[i].stride : row;
                 x.plane_offset += stride * f.height;
             }
             parse(fr, i, [&](Frame& y) {

@@ -24,32 +24,6 @@ using dev::hip_check;
 
 namespace {
 
-// offset_alignment: a power of two in [1, 4096].
-void check_alignment(uint32_t alignment)
-{
-    check_argument(alignment >= 1 && alignment <= 4096 && (alignment & (alignment - 1)) == 0);
-}
-
-uint64_t round_up(uint64_t v, uint32_t alignment)
-{
-    return (v + (alignment - 1)) & ~static_cast<uint64_t>(alignment - 1);
-}
-
-// charls_jpegls_encoder_get_estimated_destination_size for the frames of `p` (encoder_api.cpp; reference
-// src/charls_jpegls_encoder.cpp:103-114).  Parameters the encoder is going to refuse give 1: the call fails on them anyway.
-size_t estimated_stream_bytes(const charls_amd_codec_params& p)
-{
-    const charls_frame_info& f = p.frame_info;
-    if (f.width == 0 || f.width > kMaxDimension || f.height == 0 || f.height > kMaxDimension || f.component_count < 1 ||
-        f.component_count > kMaxComponents || f.bits_per_sample < kMinBits || f.bits_per_sample > kMaxBits)
-        return 1;
-    const size_t size = static_cast<size_t>(f.width) * f.height * static_cast<size_t>(f.component_count) * bytes_per_sample(f.bits_per_sample);
-    size_t extra = size / 16 + 1024 + kSpiffHeaderSize;
-    if (p.restart_interval != 0)
-        extra += 6 + 2 * static_cast<size_t>((f.height + p.restart_interval - 1) / p.restart_interval) * static_cast<size_t>(f.component_count);
-    return size + extra;
-}
-
 // GPU time of what is launched on `stream` between construction and stop_and_wait (hipEvents).
 struct LaunchTimer
 {
@@ -78,6 +52,21 @@ struct LaunchTimer
 
 } // namespace
 
+// charls_jpegls_encoder_get_estimated_destination_size for the frames of `p` (encoder_api.cpp; reference
+// src/charls_jpegls_encoder.cpp:103-114).  Parameters the encoder is going to refuse give 1: the call fails on them anyway.
+size_t jls::estimated_stream_bytes(const charls_amd_codec_params& p)
+{
+    const charls_frame_info& f = p.frame_info;
+    if (f.width == 0 || f.width > kMaxDimension || f.height == 0 || f.height > kMaxDimension || f.component_count < 1 ||
+        f.component_count > kMaxComponents || f.bits_per_sample < kMinBits || f.bits_per_sample > kMaxBits)
+        return 1;
+    const size_t size = static_cast<size_t>(f.width) * f.height * static_cast<size_t>(f.component_count) * bytes_per_sample(f.bits_per_sample);
+    size_t extra = size / 16 + 1024 + kSpiffHeaderSize;
+    if (p.restart_interval != 0)
+        extra += 6 + 2 * static_cast<size_t>((f.height + p.restart_interval - 1) / p.restart_interval) * static_cast<size_t>(f.component_count);
+    return size + extra;
+}
+
 extern "C" charls_jpegls_errc charls_amd_pack_streams_device(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
                                                              const uint64_t* sizes, void* d_packed, size_t packed_capacity_bytes,
                                                              uint32_t offset_alignment, uint64_t* offsets, void* hip_stream)
@@ -85,7 +74,7 @@ try
 {
     check_pointer(sizes);
     check_pointer(offsets);
-    check_alignment(offset_alignment);
+    check_offset_alignment(offset_alignment);
     if (frame_count == 0)
     {
         offsets[0] = 0;
@@ -109,7 +98,7 @@ try
         if (sizes[f] == 0)
             continue; // (a frame that failed takes no room)
         const uint64_t end = at + sizes[f];
-        const uint64_t next = round_up(end, offset_alignment);
+        const uint64_t next = round_up_to(end, offset_alignment);
         if (next > packed_capacity_bytes)
             raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
         jobs.push_back(PackJob{static_cast<uint64_t>(f) * stream_pitch_bytes, at, sizes[f], static_cast<uint32_t>(next - end), 0});
@@ -150,7 +139,7 @@ try
     check_pointer(offsets);
     check_pointer(sizes);
     check_pointer(errcs);
-    check_alignment(offset_alignment);
+    check_offset_alignment(offset_alignment);
     if (frame_count == 0)
     {
         offsets[0] = 0;
@@ -217,7 +206,7 @@ try
                 continue; // (a frame that failed takes no room)
             }
             const uint64_t end = at + sizes[f];
-            const uint64_t next = round_up(end, offset_alignment);
+            const uint64_t next = round_up_to(end, offset_alignment);
             // (the gap behind the last frame that fits is zeroed as far as the buffer goes)
             const uint64_t pad = std::min<uint64_t>(next, packed_capacity_bytes) - end;
             jobs[job_count++] = PackJob{static_cast<uint64_t>(i) * slot, at, sizes[f], static_cast<uint32_t>(pad), 0};

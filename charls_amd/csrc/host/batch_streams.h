@@ -1,4 +1,5 @@
-// batch_streams.h -- what the batch entry points share across translation units (batch_api.cpp, batch_packed.cpp).
+// batch_streams.h -- what the batch entry points share across translation units (batch_api.cpp, batch_packed.cpp,
+// batch_ragged.cpp).
 #pragma once
 #include <cstdint>
 
@@ -6,11 +7,55 @@
 
 namespace jls {
 
+// Where the frames of a decoder call go.  `dests[i]` is frame i's destination: its first row, the bytes the call may write
+// from there on, its stride (0 = minimal).  The slot and packed entry points state frames + i * frame_pitch_bytes, the pitch
+// and their one stride; charls_amd_decode_batch_device_ragged hands over the caller's table and sets `ragged`:
+//  * params_out is then an array, element i describing frame i (it is ONE element otherwise: the lowest-index frame that
+//    got as far as a scan), and
+//  * stride and capacity are checked against the WHOLE frame (all planes of a planar frame) once its header is parsed, so
+//    that nothing of a frame that fails either check is written; the slot calls check scan by scan, as part 1 does.
+// `dests == nullptr` is the probe (charls_amd_probe_batch_device_packed): every frame's header is fetched and parsed exactly
+// as a decode does it, params_out (an array) and frame_bytes_out are filled, and nothing is launched.
+struct BatchDests
+{
+    const charls_amd_frame_dest* dests;
+    bool ragged;
+    uint64_t* frame_bytes_out; // the probe only
+};
+
 // The batch decoder with every frame's stream named by an offset of its own: frame i's .jls is the sizes[i] bytes at
 // d_streams + stream_at[i] (HOST array; any order, any alignment, streams may abut or coincide: they are only read).
 // Raises; errcs[i] and params_out as charls_amd_decode_batch_device.  frame_count >= 1, pointers checked by the caller.
 void decode_batch_streams(uint32_t frame_count, const void* d_streams, const uint64_t* stream_at, const uint64_t* sizes,
+                          const BatchDests& to, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs, void* hip_stream);
+// The same with the frames of the slot calls: frame i at d_frames + i * frame_pitch_bytes, one stride.
+void decode_batch_streams(uint32_t frame_count, const void* d_streams, const uint64_t* stream_at, const uint64_t* sizes,
                           void* d_frames, size_t frame_pitch_bytes, uint32_t stride_arg, charls_amd_codec_params* params_out,
                           charls_jpegls_errc* errcs, void* hip_stream);
+
+// The batch encoder behind charls_amd_encode_batch_device with every frame's pixels named by a pointer of its own
+// (d_pixels: HOST array of frame_count DEVICE pointers; the slot call passes d_frames + i * frame_pitch_bytes): frame i's
+// .jls goes to d_streams + i * stream_pitch_bytes.  `frame_bytes` is what every frame offers from its pointer on (the slot
+// call's frame_pitch_bytes).  Raises -- for parameters the encoder refuses: what check_encode_params raises --; sizes and
+// errcs as charls_amd_encode_batch_device.  frame_count >= 1, pointers checked by the caller.
+void encode_batch_frames(const charls_amd_codec_params& params, uint32_t frame_count, const uint8_t* const* d_pixels,
+                         size_t frame_bytes, uint32_t stride_arg, void* d_streams, size_t stream_pitch_bytes, uint64_t* sizes,
+                         charls_jpegls_errc* errcs, void* hip_stream);
+// Raises what the batch encoder raises for these parameters before it codes anything (needs no GPU).
+void check_encode_params(const charls_amd_codec_params& params, size_t frame_bytes, uint32_t stride_arg);
+
+// charls_jpegls_encoder_get_estimated_destination_size for the frames of `p` (batch_packed.cpp).
+size_t estimated_stream_bytes(const charls_amd_codec_params& p);
+
+// offset_alignment of the packed calls: a power of two in [1, 4096].
+inline void check_offset_alignment(uint32_t alignment)
+{
+    check_argument(alignment >= 1 && alignment <= 4096 && (alignment & (alignment - 1)) == 0);
+}
+
+inline uint64_t round_up_to(uint64_t v, uint32_t alignment)
+{
+    return (v + (alignment - 1)) & ~static_cast<uint64_t>(alignment - 1);
+}
 
 } // namespace jls

@@ -563,6 +563,80 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_device_packed(uint32_t
                                                                         charls_amd_codec_params* params_out,
                                                                         charls_jpegls_errc* errcs, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Part 2e -- RAGGED frames in the batch API: the frames of ONE call may differ in geometry and coding parameters and need
+ * not share an allocation -- archives, DICOM studies with several series, tile grids with edge tiles (a tile is a pointer
+ * into the image with the image's row length as its stride), thumbnails beside full frames, lists of separately allocated
+ * tensors.  Every frame brings a table entry of its own; streams are in the packed form of part 2d on both sides (a caller
+ * who has slots passes offsets[f] = f * pitch).  `sources`, `dests`, `offsets`, `sizes`, `errcs`, `params_out` and
+ * `frame_bytes_out` are HOST arrays of frame_count elements (encode: offsets has frame_count + 1); the return value and
+ * hip_stream are those of part 2.  New entry points beside the existing ones, none of which changes.  `reserved` must be 0.
+ *
+ * probe_batch_device_packed: what the streams of a packed blob hold, WITHOUT decoding them -- a caller sizes and allocates
+ *   its destinations from it.  errcs[f] is the first code that is not success from a fresh part-1 decoder's
+ *   set_source_buffer(stream f, sizes[f]) and read_header; on success params_out[f] holds what
+ *   charls_amd_decode_batch_device_packed reports for the frame and frame_bytes_out[f] what
+ *   charls_jpegls_decoder_get_destination_size(stride 0) returns; on failure both are zeroed (as they are for an abbreviated
+ *   table-only stream, on which read_header succeeds).  The first bytes of every stream are gathered on the device and
+ *   brought over in one copy, as the batch decoders do it; no whole stream is copied to the host and no decoder is launched.
+ *   The readability rule of part 2d applies to d_packed.
+ * decode_batch_device_ragged: per frame the pixels, params_out[f] (an ARRAY here; zeroed for a frame that did not get as
+ *   far as its first scan) and the errc of charls_amd_decode_batch_device_packed, frame f going to dests[f].d_pixels with
+ *   dests[f].stride.  A stride below the frame's row is invalid_argument_stride for that frame; a capacity_bytes below
+ *   stride * rows - (stride - row) is invalid_argument_size for that frame (rows: the rows of all planes of a planar
+ *   frame).  Both are checked against the whole frame once its header is read: neither affects another frame, nothing of a
+ *   frame that fails them is written, and nothing is written outside any frame's extent.  The destinations may sit in
+ *   different allocations; destinations that overlap are the caller's error and are not looked for.  A d_pixels of NULL with
+ *   a capacity_bytes that is not 0, or a `reserved` that is not 0, is invalid_argument for the whole call.
+ * encode_batch_device_ragged: frame f gets exactly the bytes and the errc charls_amd_encode_batch_device_packed gives a
+ *   batch that holds this one frame, with sources[f].params, .stride and .max_stream_bytes, placed by the offset rule of
+ *   part 2d IN THE CALLER'S FRAME ORDER.  The capacity rule is the same: a frame whose end lies beyond
+ *   packed_capacity_bytes gets destination_too_small and so does every frame after it in the caller's order, whatever order
+ *   they were coded in.  Parameters the encoder refuses (2 > bits, a color transformation with NEAR, a stride below the
+ *   row, ...) are THAT FRAME's errc, with sizes[f] == 0 and no room taken -- not the call's return value.  Errors of the
+ *   whole call, checked before anything is done: NULL tables, a `reserved` that is not 0, a d_pixels of NULL, an
+ *   offset_alignment that is no power of two in [1, 4096].  The same pixels may be named by several frames.
+ *   How: the frames are walked in the caller's order in WINDOWS; inside a window the frames with equal params, stride and
+ *   max_stream_bytes form a group, every group is coded by the launches of charls_amd_encode_batch_device into a stretch of
+ *   staging slots of its own, and the whole window is packed by ONE launch of the copy kernel, the running offset carrying
+ *   from window to window.  The staging is the work area of charls_amd_encode_batch_device_packed under its rule (a quarter
+ *   of what the thread's work areas may hold; not_enough_memory when a configured workspace limit does not cover the
+ *   largest frame's slot).  Not done: the groups of a window run one after another, not on side streams; the indexed calls
+ *   of part 2c and the multi-device calls of part 2b stay as they are; the tile pipeline has no mixed-geometry launch (a
+ *   batch of many geometries with few frames each pays one set of launches per geometry and window).
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct charls_amd_frame_source /* encode: one frame of a ragged batch */
+{
+    charls_amd_codec_params params; /* this frame's own parameters */
+    const void* d_pixels;           /* first row, the reference's user layout for params */
+    uint32_t stride;                /* 0 = minimal */
+    uint32_t reserved;              /* must be 0 */
+    uint64_t max_stream_bytes;      /* 0 = part 1's estimated destination size of this frame */
+} charls_amd_frame_source;
+
+typedef struct charls_amd_frame_dest /* decode: where one frame goes */
+{
+    void* d_pixels;
+    uint64_t capacity_bytes; /* bytes the call may write from d_pixels on */
+    uint32_t stride;         /* 0 = minimal */
+    uint32_t reserved;       /* must be 0 */
+} charls_amd_frame_dest;
+
+CHARLS_AMD_API charls_jpegls_errc charls_amd_probe_batch_device_packed(uint32_t frame_count, const void* d_packed,
+                                                                       const uint64_t* offsets, const uint64_t* sizes,
+                                                                       charls_amd_codec_params* params_out,
+                                                                       uint64_t* frame_bytes_out, charls_jpegls_errc* errcs,
+                                                                       void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_device_ragged(uint32_t frame_count, const void* d_packed,
+                                                                        const uint64_t* offsets, const uint64_t* sizes,
+                                                                        const charls_amd_frame_dest* dests,
+                                                                        charls_amd_codec_params* params_out,
+                                                                        charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_encode_batch_device_ragged(uint32_t frame_count, const charls_amd_frame_source* sources,
+                                                                        void* d_packed, size_t packed_capacity_bytes,
+                                                                        uint32_t offset_alignment, uint64_t* offsets, uint64_t* sizes,
+                                                                        charls_jpegls_errc* errcs, void* hip_stream);
+
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */
 CHARLS_AMD_API charls_jpegls_errc charls_amd_set_encode_engine(int32_t engine);
