@@ -72,7 +72,7 @@ JLS_DEV int load_sample(const ScanDesc& d, uint32_t line, uint32_t x, int mask)
         load_pixel<S>(d, line / (uint32_t)d.components, x, mask, px);
         return px[line % (uint32_t)d.components];
     }
-    const S* row = reinterpret_cast<const S*>(d.pixels + (size_t)line * d.pixel_stride);
+    const auto row = reinterpret_cast<const JLS_GLOBAL_AS S*>(global_ptr(d.pixels) + (size_t)line * d.pixel_stride);
     return (int)row[x] & mask;
 }
 

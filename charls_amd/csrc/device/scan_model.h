@@ -40,6 +40,13 @@ extern "C" unsigned long long jls_path_counts[32];
 #ifndef JLS_GLOBAL_AS
 #define JLS_GLOBAL_AS __attribute__((address_space(1)))
 #endif
+// The cast itself, for a pointer that is known to point into device memory (work areas, pixels, streams; never LDS): the
+// kernels apply it where they take such a pointer out of a descriptor.  The identity in the CPU test harness.
+template <typename T>
+JLS_DEV JLS_GLOBAL_AS T* global_ptr(T* p)
+{
+    return (JLS_GLOBAL_AS T*)p;
+}
 
 // Launch-time sized LDS (Guideline 17 of the CDNA guide: everything carved from one 16-byte aligned dynamic region).
 // The CPU test harness pre-defines this to point at its per-workgroup buffer.
@@ -242,6 +249,14 @@ JLS_DEV uint64_t load_relaxed(const uint64_t* p)
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 JLS_DEV void store_relaxed(uint64_t* p, uint64_t v)
+{
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+JLS_DEV uint64_t load_relaxed(const JLS_GLOBAL_AS uint64_t* p) // (global_ptr: the same word through global_* instructions)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+JLS_DEV void store_relaxed(JLS_GLOBAL_AS uint64_t* p, uint64_t v)
 {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -367,7 +367,7 @@ JLS_DEV void stage_lines(const ScanDesc& d, const TileGeometry& g, S* rows)
     if (first)
         for (uint32_t x = threadIdx.x; x < width; x += blockDim.x)
             rows[x] = 0; // src/scan_encoder_impl.hpp:55-70
-    const uint8_t* from = d.pixels + (size_t)(g.first_line + first - 1) * d.pixel_stride;
+    const auto from = global_ptr(d.pixels) + (size_t)(g.first_line + first - 1) * d.pixel_stride;
     uint8_t* to = reinterpret_cast<uint8_t*>(rows) + (size_t)first * bytes;
     const uint32_t lines = g.tile_lines + 1 - first;
     if (((reinterpret_cast<uintptr_t>(from) | d.pixel_stride | bytes) & 3u) == 0 && (reinterpret_cast<uintptr_t>(to) & 3u) == 0)
@@ -383,7 +383,7 @@ JLS_DEV void stage_lines(const ScanDesc& d, const TileGeometry& g, S* rows)
 #pragma unroll
         for (int j = 0; j < kMost; ++j)
         {
-            held[j] = line < lines ? reinterpret_cast<const uint32_t*>(from + (size_t)line * d.pixel_stride)[word] : 0u;
+            held[j] = line < lines ? reinterpret_cast<const JLS_GLOBAL_AS uint32_t*>(from + (size_t)line * d.pixel_stride)[word] : 0u;
             line += step_lines;
             word += step_words;
             if (word >= words_per_line)
@@ -402,13 +402,13 @@ JLS_DEV void stage_lines(const ScanDesc& d, const TileGeometry& g, S* rows)
         for (uint32_t i = threadIdx.x + kMost * kThreads; i < total; i += kThreads) // (tiles of many short lines of wide samples)
         {
             const uint32_t l2 = i / words_per_line, w2 = i - l2 * words_per_line;
-            reinterpret_cast<uint32_t*>(to)[i] = reinterpret_cast<const uint32_t*>(from + (size_t)l2 * d.pixel_stride)[w2];
+            reinterpret_cast<uint32_t*>(to)[i] = reinterpret_cast<const JLS_GLOBAL_AS uint32_t*>(from + (size_t)l2 * d.pixel_stride)[w2];
         }
     }
     else
         for (uint32_t r = 0; r < lines; ++r)
         {
-            const S* from1 = reinterpret_cast<const S*>(from + (size_t)r * d.pixel_stride);
+            const auto from1 = reinterpret_cast<const JLS_GLOBAL_AS S*>(from + (size_t)r * d.pixel_stride);
             S* to1 = reinterpret_cast<S*>(to + (size_t)r * bytes);
             for (uint32_t x = threadIdx.x; x < width; x += blockDim.x)
                 to1[x] = from1[x];
@@ -529,7 +529,7 @@ __global__ void __launch_bounds__(kThreads) analyze_tiles(const ScanDesc* __rest
         const uint32_t y = g.first_line + r;
         const uint32_t k0 = piece * g.chunks_per_piece;
         const uint32_t k1 = k0 + g.chunks_per_piece < chunks ? k0 + g.chunks_per_piece : chunks;
-        uint16_t* key_row = w.keyinv + (size_t)y * width;
+        const auto key_row = global_ptr(w.keyinv) + (size_t)y * width;
         unsigned long long carry = 0;
         for (uint32_t k = 0; k < k1; ++k)
         {
@@ -565,7 +565,7 @@ __global__ void __launch_bounds__(kThreads) analyze_tiles(const ScanDesc* __rest
     }
     __syncthreads();
     for (uint32_t c = threadIdx.x; c < (uint32_t)kChains; c += kThreads)
-        w.seg[(size_t)tile * kChains + c] = s_hist[c];
+        global_ptr(w.seg)[(size_t)tile * kChains + c] = s_hist[c];
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -755,7 +755,7 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
     Slot<S>* s_stage = reinterpret_cast<Slot<S>*>(s_rowbase + kChains + 1 + kRowChainWords);
     const int mask = (1 << d.bits_per_sample) - 1;
     const Samples<S, ILV> sample{d, s_rows, g.first_line, mask};
-    const uint16_t* key_tile = w.keyinv + (size_t)g.first_line * width;
+    const auto key_tile = global_ptr(w.keyinv) + (size_t)g.first_line * width; // (read as keys, written as slots: P2)
 
     JLS_PHASE_BEGIN();
     stage_lines<S, ILV>(d, g, s_rows);
@@ -766,32 +766,52 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
         s_same[i] = 0;
     __syncthreads();
     JLS_PHASE(1);
-    // ---- P1: keys into LDS, events per (segment, chain), samples inside runs per chunk
+    // ---- P1: events per (segment, chain), samples inside runs per chunk.  The keys of up to 16 chunks are requested before
+    // the first one is used (one trip to memory, not sixteen) and packed two to a register: chunk kb + j in half j & 1 of
+    // keys2[j / 2].  Where a wavefront has ONE segment of at most 16 chunks (keys_kept: 4096 x 2, 8192 x 1, 2048 x 4,
+    // 1024 x 8 and most other shapes) the eight registers live through the offsets phase into P2, which then reads no key
+    // from memory at all.
+    const bool keys_kept = g.segments <= kWaves && g.chunks_per_piece <= 16;
+    uint32_t keys2[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        keys2[i] = 0xFFFFFFFFu; // (kNoEvent twice)
+    auto fetch_keys = [&](uint32_t r, uint32_t kb, uint32_t k1) {
+        // (every lane loads in every chunk, from the line's last sample where it has none: sixteen loads with nothing
+        // between them -- loads under a condition came out as sixteen branches with a wait behind every other one)
+        uint32_t held[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+        {
+            const uint32_t x = (kb + j) * 64 + lane;
+            held[j] = key_tile[(size_t)r * width + (x < width ? x : width - 1)];
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (!(kb + j < k1 && (kb + j) * 64 + lane < width))
+                held[j] = kNoEvent;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            keys2[i] = held[2 * i] | (held[2 * i + 1] << 16);
+    };
     for (uint32_t sgm = wave; sgm < g.segments; sgm += kWaves)
     {
         const uint32_t r = sgm / g.pieces, piece = sgm % g.pieces;
         const uint32_t k0 = piece * g.chunks_per_piece;
         const uint32_t k1 = k0 + g.chunks_per_piece < chunks ? k0 + g.chunks_per_piece : chunks;
         for (uint32_t kb = k0; kb < k1; kb += 16)
-        { // the keys of up to 16 chunks are requested before the first one is used (one trip to memory, not sixteen)
-            uint16_t held[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-            {
-                const uint32_t x = (kb + j) * 64 + lane;
-                held[j] = kb + j < k1 && x < width ? key_tile[(size_t)r * width + x] : kNoEvent;
-            }
+        {
+            fetch_keys(r, kb, k1);
 #pragma unroll
             for (int j = 0; j < 16; ++j)
             {
                 const uint32_t k = kb + j;
                 if (k < k1) // (uniform)
                 {
-                    const uint32_t x = k * 64 + lane;
-                    const uint16_t key = held[j];
-                    if (x < width && key != kNoEvent)
+                    const uint16_t key = (uint16_t)(keys2[j >> 1] >> ((j & 1) * 16)); // (kNoEvent beyond the line's end)
+                    if (key != kNoEvent)
                         atomicAdd(&s_segoff[sgm * kChains + (key & 0x1FF)], (key & 0x1FF) == 0 ? run_slots_of<S>() : 1u); // (slots)
-                    const unsigned long long m = __ballot(x < width && key == kNoEvent);
+                    const unsigned long long m = __ballot(k * 64 + lane < width && key == kNoEvent);
                     if (lane == 0)
                         s_noev[r * chunks + k] = m;
                 }
@@ -850,7 +870,7 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
         {
             s_tileoff[c] = off[0];
             s_count[c] = n;
-            s_global[c] = w.seg[(size_t)tile * kChains + c];
+            s_global[c] = global_ptr(w.seg)[(size_t)tile * kChains + c];
             uint32_t running = off[0];
             for (uint32_t sgm = 0; sgm < g.segments; ++sgm)
             {
@@ -872,6 +892,18 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
     // ORs its own bit into the word of its chain (the result does not depend on the order in which the LDS serves the
     // lanes), reads the word back and clears it -- 32 lanes at a time, six LDS instructions per chunk where a ballot per
     // key bit took some sixty vector and scalar ones, and this stage is bound by the instructions it issues.
+    //
+    // Memory stays off the chunk loop.  The keys of a batch of 16 chunks are in keys2 (from P1 where keys_kept; requested
+    // together otherwise -- the keys are not kept in LDS: 16 KB that decide between one and two workgroups per CU); every
+    // trip shifts the registers down by one key and shifts the chunk's tile-local slot in at the top, so that behind the
+    // batch keys2 holds its sixteen slots, which then leave back to back: no load and no store between two chunks.
+    //
+    // Run starts stay off it too.  A lane with a run start takes part in the rank like any other and leaves its COLUMN in
+    // its slot of s_stage; behind the segment's chunks the wavefront takes the segment's run starts 64 at a time, a lane
+    // each, and turns the columns into run records.  The slots say where they are: chain 0's events of a segment are ranked
+    // in raster order, so they are the entries from the segment's first chain-0 slot (s_segoff before the loop moves it)
+    // to where the loop left it.  (Until round 12 one run start among the 64 lanes sent the whole wavefront through the
+    // record block, 100 to 190 instructions, in more than half of the bench's chunks and in every chunk of a photograph.)
     for (uint32_t sgm = wave; sgm < g.segments; sgm += kWaves)
     {
         const uint32_t r = sgm / g.pieces, piece = sgm % g.pieces;
@@ -880,93 +912,114 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
         const uint32_t k1 = k0 + g.chunks_per_piece < chunks ? k0 + g.chunks_per_piece : chunks;
         uint32_t* segoff = s_segoff + sgm * kChains;
         uint32_t* same_of = s_same + (uint32_t)wave * (kChains + 1);
-        uint16_t* inv_row = w.keyinv + (size_t)y * width; // the key of a sample is read here and its slot written in its place
-        // (the keys are not kept in LDS -- 16 KB that decide between one and two workgroups per CU: they are read again,
-        // two chunks ahead of their use)
-        auto key_at = [&](uint32_t k) -> uint16_t {
-            const uint32_t x = k * 64 + lane;
-            return k < k1 && x < width ? inv_row[x] : kNoEvent;
-        };
-        uint16_t key_1 = key_at(k0), key_2 = key_at(k0 + 1);
+        const auto inv_row = key_tile + (size_t)r * width; // the key of a sample was read here; its slot is written in its place
         const S* cur = s_rows + (r + 1) * width; // (planar scans: the line in LDS, the line above it `width` samples before)
         const int edge_a = y >= step ? sample(y - step, 0) : 0;
         const int edge_c = y >= 2 * step ? (r >= 1 ? sample(y - 2 * step, 0) : pipe::load_sample<S, 0>(d, y - 2, 0, mask)) : 0;
         const uint32_t lane_bit = 1u << (lane & 31), below = lane_bit - 1u;
         const bool upper = lane >= 32;
-        for (uint32_t k = k0; k < k1; ++k)
+        const uint32_t run_first = segoff[0];
+        for (uint32_t kb = k0; kb < k1; kb += 16)
         {
-            const uint32_t x = k * 64 + lane;
-            const bool inside = x < width;
-            const uint16_t key = key_1;
-            key_1 = key_2;
-            key_2 = key_at(k + 2);
-            const bool has = key != kNoEvent;
-            const uint32_t chain = key & 0x1FFu;
-            if (has && !upper)
-                atomicOr(&same_of[chain], lane_bit);
-            JLS_LOCKSTEP();
-            const uint32_t lo = has ? same_of[chain] : 0u;
-            JLS_LOCKSTEP();
-            if (has && !upper)
-                same_of[chain] = 0;
-            JLS_LOCKSTEP();
-            if (has && upper)
-                atomicOr(&same_of[chain], lane_bit);
-            JLS_LOCKSTEP();
-            const uint32_t hi = has ? same_of[chain] : 0u;
-            const uint32_t base = has ? segoff[chain] : 0u;
-            JLS_LOCKSTEP();
-            if (has && upper)
-                same_of[chain] = 0;
-            const uint32_t rank = upper ? (uint32_t)__popc(lo) + (uint32_t)__popc(hi & below) : (uint32_t)__popc(lo & below);
-            const uint32_t per_event = chain == 0 ? run_slots_of<S>() : 1u; // slots an event of this chain takes
-            if (has && rank == 0)
-                segoff[chain] = base + ((uint32_t)__popc(lo) + (uint32_t)__popc(hi)) * per_event;
-            JLS_LOCKSTEP();
-            const uint32_t slot = base + rank * per_event;
-            // the record of a regular sample, worked out for every lane (no divergence; lanes without an event discard it)
-            uint32_t record = 0;
-            if (inside)
+            if (!keys_kept)
+                fetch_keys(r, kb, k1);
+            const uint32_t batch = k1 - kb < 16u ? k1 - kb : 16u;
+            for (uint32_t j = 0; j < 16; ++j)
             {
-                const int v = (int)cur[x] & mask;
-                const int ra = x > 0 ? (int)cur[x - 1] & mask : edge_a;
-                const int rb = (int)(cur - width)[x] & mask;
-                const int rc = x > 0 ? (int)(cur - width)[x - 1] & mask : edge_c;
-                record = make_record<S>(v, med3(ra + rb - rc, ra, rb), (key >> 9) & 1, t.maxval);
-            }
-            if (__any(has && chain == 0))
-            { // (rare) run starts
-                if (has && chain == 0)
+                uint32_t out = kNoLocalSlot;
+                if (j < batch) // (uniform; a short batch shifts on until its slots sit where a full batch has them)
                 {
-                    const int v = sample(y, x);
-                    const int ra = x > 0 ? sample(y, x - 1) : edge_a;
-                    uint32_t run = 0;
-                    if (v == ra)
+                    const uint32_t x = (kb + j) * 64 + lane;
+                    const bool inside = x < width;
+                    const uint32_t key = keys2[0] & 0xFFFFu;
+                    const bool has = key != kNoEvent;
+                    const uint32_t chain = key & 0x1FFu;
+                    if (has && !upper)
+                        atomicOr(&same_of[chain], lane_bit);
+                    JLS_LOCKSTEP();
+                    const uint32_t lo = has ? same_of[chain] : 0u;
+                    JLS_LOCKSTEP();
+                    if (has && !upper)
+                        same_of[chain] = 0;
+                    JLS_LOCKSTEP();
+                    if (has && upper)
+                        atomicOr(&same_of[chain], lane_bit);
+                    JLS_LOCKSTEP();
+                    const uint32_t hi = has ? same_of[chain] : 0u;
+                    const uint32_t base = has ? segoff[chain] : 0u;
+                    JLS_LOCKSTEP();
+                    if (has && upper)
+                        same_of[chain] = 0;
+                    const uint32_t rank = upper ? (uint32_t)__popc(lo) + (uint32_t)__popc(hi & below) : (uint32_t)__popc(lo & below);
+                    const uint32_t per_event = chain == 0 ? run_slots_of<S>() : 1u; // slots an event of this chain takes
+                    if (has && rank == 0)
+                        segoff[chain] = base + ((uint32_t)__popc(lo) + (uint32_t)__popc(hi)) * per_event;
+                    JLS_LOCKSTEP();
+                    const uint32_t slot = base + rank * per_event;
+                    // the record of a regular sample, worked out for every lane (no divergence; lanes without an event discard
+                    // it); a run start leaves its column (the second of its two 2-byte slots is written with the record)
+                    uint32_t record = 0;
+                    if (inside)
                     {
-                        const unsigned long long after = lane == 63 ? 0ull : s_noev[r * chunks + k] >> (lane + 1);
-                        const uint32_t rest = 63u - (uint32_t)lane;
-                        uint32_t n = (uint32_t)__ffsll(~after) - 1;
-                        if (n >= rest)
-                            n = rest + s_lead[r * (chunks + 1) + k + 1];
-                        run = 1 + n;
+                        const int v = (int)cur[x] & mask;
+                        const int ra = x > 0 ? (int)cur[x - 1] & mask : edge_a;
+                        const int rb = (int)(cur - width)[x] & mask;
+                        const int rc = x > 0 ? (int)(cur - width)[x - 1] & mask : edge_c;
+                        record = make_record<S>(v, med3(ra + rb - rc, ra, rb), (key >> 9) & 1, t.maxval);
                     }
-                    const uint32_t xi = x + run;
-                    if (xi >= width)
-                        record = RunRecord<S>::end_of_line(run, 0u);
-                    else
-                    {
-                        const int xv = sample(y, xi);
-                        const int ia = xi > 0 ? sample(y, xi - 1) : edge_a;
-                        const int ib = y >= step ? sample(y - step, xi) : 0;
-                        const int which = ia == ib ? 1 : 0;
-                        const int err = which ? error_value(t, xv - ia) : error_value(t, (xv - ib) * ((ib - ia) < 0 ? -1 : 1));
-                        record = RunRecord<S>::interrupted(run, err, which, 0u);
-                    }
+                    if (has)
+                        s_stage[slot] = (Slot<S>)(chain == 0 ? x : record);
+                    out = has ? slot : (uint32_t)kNoLocalSlot;
                 }
+#pragma unroll
+                for (int i = 0; i < 7; ++i)
+                    keys2[i] = (keys2[i] >> 16) | (keys2[i + 1] << 16);
+                keys2[7] = (keys2[7] >> 16) | (out << 16);
             }
-            if (has)
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
             {
-                if (run_slots_of<S>() == 2 && chain == 0)
+                const uint32_t x = (kb + j) * 64 + lane;
+                if (kb + j < k1 && x < width)
+                    inv_row[x] = (uint16_t)(keys2[j >> 1] >> ((j & 1) * 16));
+            }
+        }
+        // ---- the segment's run starts, 64 at a time
+        JLS_LOCKSTEP();
+        const uint32_t run_end = segoff[0];
+        for (uint32_t first = run_first; first < run_end; first += 64 * run_slots_of<S>())
+        {
+            const uint32_t slot = first + (uint32_t)lane * run_slots_of<S>();
+            if (slot < run_end)
+            {
+                const uint32_t x = (uint32_t)s_stage[slot];
+                const uint32_t k = x >> 6, bit = x & 63u;
+                const int v = sample(y, x);
+                const int ra = x > 0 ? sample(y, x - 1) : edge_a;
+                uint32_t run = 0;
+                if (v == ra)
+                {
+                    const unsigned long long after = bit == 63 ? 0ull : s_noev[r * chunks + k] >> (bit + 1);
+                    const uint32_t rest = 63u - bit;
+                    uint32_t n = (uint32_t)__ffsll(~after) - 1;
+                    if (n >= rest)
+                        n = rest + s_lead[r * (chunks + 1) + k + 1];
+                    run = 1 + n;
+                }
+                const uint32_t xi = x + run;
+                uint32_t record;
+                if (xi >= width)
+                    record = RunRecord<S>::end_of_line(run, 0u);
+                else
+                {
+                    const int xv = sample(y, xi);
+                    const int ia = xi > 0 ? sample(y, xi - 1) : edge_a;
+                    const int ib = y >= step ? sample(y - step, xi) : 0;
+                    const int which = ia == ib ? 1 : 0;
+                    const int err = which ? error_value(t, xv - ia) : error_value(t, (xv - ib) * ((ib - ia) < 0 ? -1 : 1));
+                    record = RunRecord<S>::interrupted(run, err, which, 0u);
+                }
+                if (run_slots_of<S>() == 2)
                 { // a run record: 32 bits in two slots
                     s_stage[slot] = (Slot<S>)(record & 0xFFFFu);
                     s_stage[slot + 1] = (Slot<S>)(record >> 16);
@@ -974,8 +1027,6 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
                 else
                     s_stage[slot] = (Slot<S>)record;
             }
-            if (inside)
-                inv_row[x] = has ? (uint16_t)slot : kNoLocalSlot;
         }
     }
     JLS_PHASE(6);
@@ -1002,7 +1053,7 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
 #pragma unroll
         for (int j = 0; j < kRows; ++j)
             if (live[j])
-                rec_slots<S>(w)[to[j]] = held[j];
+                global_ptr(rec_slots<S>(w))[to[j]] = held[j];
     }
     JLS_PHASE(8);
 }
@@ -1943,10 +1994,7 @@ JLS_DEV uint32_t shifted_word(const uint32_t* bits, uint32_t i, uint32_t head, u
     return (i == 0 ? carry : bits[i - 1] << (32u - head)) | (bits[i] >> head);
 }
 
-struct __attribute__((packed)) UnalignedQuadPair
-{
-    uint64_t lo, hi;
-};
+typedef uint32_t UnalignedWords4 __attribute__((vector_size(16), aligned(2))); // (eight 2-byte slots, wherever they start)
 template <typename S>
 __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __restrict__ descs, const Work* __restrict__ works)
 {
@@ -1975,7 +2023,7 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
     uint32_t* s_bits = reinterpret_cast<uint32_t*>(smem + pack_bits_offset(tile_capacity, (uint32_t)sizeof(S))); // [pack_bits_words] the tile's bits
     const TileSpan span = tile_span(d, w, tile);
     const uint32_t tile_samples = span.count;
-    const uint16_t* inv = w.keyinv + span.first;
+    const auto inv = global_ptr(w.keyinv) + span.first;
 
     // the slot map of this thread's samples: 16 bytes (eight slots) per load, straight into registers and requested before
     // anything else (lane by lane and two bytes at a time these were 32 requests of one cache line each per wavefront
@@ -1990,8 +2038,8 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
         mine[q] = make_uint4(~0u, ~0u, ~0u, ~0u);
         if ((uint32_t)q * 8 < per_thread && at + 8 <= tile_samples)
         {
-            const UnalignedQuadPair v = *reinterpret_cast<const UnalignedQuadPair*>(inv + at);
-            mine[q] = make_uint4((uint32_t)v.lo, (uint32_t)(v.lo >> 32), (uint32_t)v.hi, (uint32_t)(v.hi >> 32));
+            const UnalignedWords4 v = *reinterpret_cast<const JLS_GLOBAL_AS UnalignedWords4*>(inv + at);
+            mine[q] = make_uint4(v[0], v[1], v[2], v[3]);
         }
         else if ((uint32_t)q * 8 < per_thread && at < tile_samples)
         { // (the tile's last, partial group)
@@ -2011,8 +2059,8 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
             const uint32_t c = threadIdx.x + (uint32_t)half * threads;
             if (c < (uint32_t)kChains)
             {
-                g[half] = w.seg[(size_t)tile * kChains + c];
-                n[half] = w.seg[(size_t)(tile + 1) * kChains + c] - g[half];
+                g[half] = global_ptr(w.seg)[(size_t)tile * kChains + c];
+                n[half] = global_ptr(w.seg)[(size_t)(tile + 1) * kChains + c] - g[half];
                 rows[half] = (n[half] + 63) / 64;
             }
         }
@@ -2055,7 +2103,7 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
                 const uint32_t i = (q - s_rowbase[c]) * 64 + (uint32_t)lane;
                 live[j] = q < total_rows && i < s_count[c];
                 to[j] = s_tileoff[c] + i;
-                held[j] = live[j] ? code_slots<S>(w)[s_global[c] + i] : (Slot<S>)0;
+                held[j] = live[j] ? global_ptr(code_slots<S>(w))[s_global[c] + i] : (Slot<S>)0;
             }
 #pragma unroll
             for (int j = 0; j < kRows; ++j)
@@ -2125,7 +2173,7 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
     // this one began is applied on the way out (shifted_word).
     const uint32_t tile_bits = s_scan[threads - 1];
     if (threadIdx.x == 0)
-        store_relaxed(&w.blockbase[tile], (tile == 0 ? pipe::kBlockUpTo : pipe::kBlockOwn) | (uint64_t)tile_bits);
+        store_relaxed(&global_ptr(w.blockbase)[tile], (tile == 0 ? pipe::kBlockUpTo : pipe::kBlockOwn) | (uint64_t)tile_bits);
     // s_bits holds pack_bits_words = tile_capacity * LIMIT / 32 + 2 words and a code has at most LIMIT bits per sample it stands
     // for, so local_words + 1 <= pack_bits_words.  Words [0, local_words] are zeroed here; the assembly writes words [0,
     // local_words), and shifted_word reads bits[tile_words - 1] at most, which is bits[local_words] at most (tile_words =
@@ -2204,7 +2252,7 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
             uint64_t state = 0;
             do
             {
-                state = in_window ? load_relaxed(&w.blockbase[j]) : pipe::kBlockOwn;
+                state = in_window ? load_relaxed(&global_ptr(w.blockbase)[j]) : pipe::kBlockOwn;
             } while (__any((state >> 62) == 0));
             const unsigned long long knows = __ballot(in_window && (state >> 62) == 2);
             const int last = knows ? (int)__ffsll(knows) - 1 : 63;
@@ -2219,9 +2267,9 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
         if (lane == 0)
         {
             if (b != 0)
-                store_relaxed(&w.blockbase[b], pipe::kBlockUpTo | (start + own));
+                store_relaxed(&global_ptr(w.blockbase)[b], pipe::kBlockUpTo | (start + own));
             if (b + 1 == tiles)
-                *w.total_bits = start + own;
+                *global_ptr(w.total_bits) = start + own;
             const uint32_t head = (uint32_t)(start & 31);
             const uint32_t tile_words = (head + tile_bits + 31) / 32;
             const bool shared_first = head != 0;                                     // my first word starts in the tile before
@@ -2230,18 +2278,18 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
             // predecessor left, plus its own bits)
             const bool own_tail = tile_words >= 2 || !shared_first;
             if (own_tail)
-                store_relaxed(&w.tile_tail[tile], kTailValid | (partial_last ? shifted_word(s_bits, tile_words - 1, head, 0u) : 0u));
+                store_relaxed(&global_ptr(w.tile_tail)[tile], kTailValid | (partial_last ? shifted_word(s_bits, tile_words - 1, head, 0u) : 0u));
             uint32_t carry = 0; // the bits of my first word that the tile before me left
             if (shared_first)
             { // (tile 0 starts at bit 0)
                 uint64_t before;
                 do
-                    before = load_relaxed(&w.tile_tail[tile - 1]);
+                    before = load_relaxed(&global_ptr(w.tile_tail)[tile - 1]);
                 while ((before & kTailValid) == 0);
                 carry = (uint32_t)before;
             }
             if (!own_tail)
-                store_relaxed(&w.tile_tail[tile], kTailValid | (partial_last ? shifted_word(s_bits, 0, head, carry) : 0u));
+                store_relaxed(&global_ptr(w.tile_tail)[tile], kTailValid | (partial_last ? shifted_word(s_bits, 0, head, carry) : 0u));
             s_tmp[12] = (uint32_t)start; // (three words of the scan scratch: the kernel has no static LDS, its dynamic
             s_tmp[13] = (uint32_t)(start >> 32); // region may then be as large as the CU's)
             s_tmp[14] = carry;
@@ -2260,13 +2308,13 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
     {
         const uint64_t at = first_global + i;
         if (at < w.raw_words)
-            w.raw[at] = __builtin_bswap32(shifted_word(s_bits, i, head, carry));
+            global_ptr(w.raw)[at] = __builtin_bswap32(shifted_word(s_bits, i, head, carry));
     }
     if (last_tile && threadIdx.x < 4)
     { // the stuffing stage reads a few bytes past the last bit: zeros
         const uint64_t at = first_global + tile_words + threadIdx.x;
         if (at < w.raw_words)
-            w.raw[at] = 0;
+            global_ptr(w.raw)[at] = 0;
     }
     JLS_PHASE(21);
 }
