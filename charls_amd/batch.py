@@ -102,6 +102,14 @@ def _bind(lib):
     l.charls_amd_encode_batch_device_ragged.argtypes = [C.c_uint32, C.POINTER(FrameSource), C.c_void_p, C.c_size_t, C.c_uint32, u64p, u64p,
                                                         i32p, C.c_void_p]
     l.charls_amd_encode_batch_device_ragged.restype = C.c_int32
+    l.charls_amd_measure_batch_device.argtypes = [C.POINTER(CodecParams), C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, i32p, C.c_uint32,
+                                                  u64p, C.c_void_p]
+    l.charls_amd_measure_batch_device.restype = C.c_int32
+    l.charls_amd_encode_batch_device_budget.argtypes = [C.POINTER(CodecParams), C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, u64p, i32p,
+                                                        C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, u64p, u64p, i32p, i32p, C.c_void_p]
+    l.charls_amd_encode_batch_device_budget.restype = C.c_int32
+    l.charls_amd_measure_counters.argtypes = [u64p, C.c_int32]
+    l.charls_amd_measure_counters.restype = C.c_int32
     l._batch_bound = True
     return l
 
@@ -512,6 +520,87 @@ def encode_batch_ragged(frames, params, packed, *, alignment=1, strides=None, ma
     if rc != 0:
         raise capi.JpegLSError(rc, "charls_amd_encode_batch_device_ragged")
     return PackedBatch(packed, offsets, sizes, errcs)
+
+
+# ---- encoding to a byte budget (charls_amd.h part 2f): sizes without streams, NEAR picked per frame ------------------------
+
+def _uniform_frames(frames, width, height, frame_pitch, component_count, interleave_mode):
+    """(count, width, height, frame pitch in bytes) of a batch tensor as encode_batch takes it; width / height / frame_pitch
+    given by the caller win (frames with padded rows, frames at some offset of a byte tensor)."""
+    count = frames.shape[0]
+    if width is None or height is None:
+        if component_count == 1 or interleave_mode == 0:
+            height, width = frames.shape[-2], frames.shape[-1]
+        else:
+            height, width = frames.shape[1], frames.shape[2]
+    if frame_pitch is None:
+        frame_pitch = frames[0].numel() * frames.element_size() if count else 0
+    return count, int(width), int(height), int(frame_pitch)
+
+
+def measure_batch(frames, near_candidates, *, bits_per_sample=8, component_count=1, interleave_mode=0, color_transformation=0,
+                  preset=(0, 0, 0, 0, 0), encoding_options=0, restart_interval=0, stride=0, width=None, height=None, frame_pitch=None,
+                  lib=None) -> np.ndarray:
+    """charls_amd_measure_batch_device: sizes[f, c] = the bytes of frame f's complete .jls at NEAR near_candidates[c], what
+    encode_batch_packed reports for it, without writing any stream.  frames as for encode_batch."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert frames.is_cuda and frames.is_contiguous()
+    count, width, height, frame_pitch = _uniform_frames(frames, width, height, frame_pitch, component_count, interleave_mode)
+    nears = np.ascontiguousarray(near_candidates, dtype=np.int32)
+    p = CodecParams(capi.FrameInfo(width, height, bits_per_sample, component_count), 0, interleave_mode, color_transformation,
+                    capi.PcParameters(*preset), encoding_options, restart_interval)
+    sizes = np.zeros((count, len(nears)), dtype=np.uint64)
+    stream = torch.cuda.current_stream(frames.device).cuda_stream
+    rc = l.charls_amd_measure_batch_device(C.byref(p), count, frames.data_ptr(), frame_pitch, int(stride), nears.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           len(nears), sizes.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_measure_batch_device")
+    return sizes
+
+
+def encode_batch_budget(frames, budgets, near_candidates, packed, *, alignment=1, capacity=None, bits_per_sample=8, component_count=1,
+                        interleave_mode=0, color_transformation=0, preset=(0, 0, 0, 0, 0), encoding_options=0, restart_interval=0,
+                        stride=0, width=None, height=None, frame_pitch=None, lib=None):
+    """charls_amd_encode_batch_device_budget: every frame coded at the first NEAR of near_candidates (the order given is the
+    order of preference) whose complete stream has at most budgets[f] bytes, the streams back to back in `packed` as
+    encode_batch_packed places them.  Returns (PackedBatch, nears): nears[f] = -1, sizes[f] = 0 and errcs[f] =
+    destination_too_small for a frame that no candidate fits."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert frames.is_cuda and frames.is_contiguous() and packed.is_cuda and packed.is_contiguous()
+    count, width, height, frame_pitch = _uniform_frames(frames, width, height, frame_pitch, component_count, interleave_mode)
+    nears = np.ascontiguousarray(near_candidates, dtype=np.int32)
+    budgets = np.ascontiguousarray(budgets, dtype=np.uint64)
+    assert len(budgets) == count
+    p = CodecParams(capi.FrameInfo(width, height, bits_per_sample, component_count), 0, interleave_mode, color_transformation,
+                    capi.PcParameters(*preset), encoding_options, restart_interval)
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    sizes = np.zeros(count, dtype=np.uint64)
+    chosen = np.zeros(count, dtype=np.int32)
+    errcs = np.zeros(count, dtype=np.int32)
+    stream = torch.cuda.current_stream(frames.device).cuda_stream
+    u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    rc = l.charls_amd_encode_batch_device_budget(C.byref(p), count, frames.data_ptr(), frame_pitch, int(stride), budgets.ctypes.data_as(u64p),
+                                                 nears.ctypes.data_as(i32p), len(nears), packed.data_ptr(),
+                                                 packed.numel() if capacity is None else int(capacity), alignment,
+                                                 offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p), chosen.ctypes.data_as(i32p),
+                                                 errcs.ctypes.data_as(i32p), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_encode_batch_device_budget")
+    return PackedBatch(packed, offsets, sizes, errcs), chosen
+
+
+def measure_counters(lib=None):
+    """charls_amd_measure_counters: (scans sized by the measuring kernels, launches of them, scans sized by coding them for
+    real), process-wide since the library was loaded."""
+    l = _bind(lib or capi.load_product())
+    out = (C.c_uint64 * 3)()
+    n = l.charls_amd_measure_counters(out, 3)
+    assert n == 3
+    return tuple(int(out[i]) for i in range(3))
 
 
 def set_workspace_limit(nbytes: int, lib=None):

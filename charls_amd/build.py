@@ -25,6 +25,8 @@ SOURCES = [
     "device/launch_pixels_u16.hip",
     "device/launch_group_encode_u8.hip",
     "device/launch_group_encode_u16.hip",
+    "device/launch_group_measure_u8.hip",
+    "device/launch_group_measure_u16.hip",
     "device/seek_launch.hip",
     "device/segment_hash.hip",
     "device/pack_streams.hip",
@@ -38,6 +40,7 @@ SOURCES = [
     "host/batch_index.cpp",
     "host/batch_packed.cpp",
     "host/batch_ragged.cpp",
+    "host/batch_budget.cpp",
     "host/multi_device.cpp",
 ]
 

@@ -24,5 +24,10 @@ void launch_decode_pixels(const ScanDesc& proto, int lanes, const ScanDesc* d_de
 size_t group_encode_lds_bytes(const ScanDesc& d, uint32_t scans_per_wave);
 void launch_encode_group(const ScanDesc& proto, int lanes, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
                          hipStream_t stream);
+// its measuring form (launch_group_measure.inc): ScanResult::bytes is the length of the segment launch_encode_group writes for
+// the same descriptors; stream, stream_capacity and line_scratch of the descriptors are not looked at.  The LDS is
+// group_encode_lds_bytes.
+void launch_measure_group(const ScanDesc& proto, int lanes, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
+                          hipStream_t stream);
 
 } // namespace jls::dev

@@ -116,6 +116,12 @@ void launch_decode(const ScanDesc& proto, const ScanDesc* d_descs, ScanResult* d
 // whose destination is within 3 bytes of its output size, runs the exact one-wavefront-per-scan kernel.
 bool pipeline_eligible(const ScanDesc& proto) noexcept;
 void launch_encode(const ScanDesc& proto, ScanDesc* d_descs, ScanResult* d_results, uint32_t count, hipStream_t stream);
+// Sizing dispatch: the measuring form of the group encoder (scan_group_encode.hip, kMeasure) over `count` scans that share
+// proto's geometry and coding mode -- NEAR, thresholds and RESET may differ from scan to scan -- with the lanes per scan that
+// the encoder's rule gives for `count` chains.  results[i].bytes is the length of scan i's entropy-coded segment whatever
+// engine would code it.  False, and nothing launched: scans the group encoder does not take (lines beyond LDS, the engine
+// forced to serial, restart intervals).
+bool launch_measure(const ScanDesc& proto, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count, hipStream_t stream);
 
 // Container placement kernels (container_kernels.hip); all pointers are DEVICE pointers.
 struct FrameCursorPod

@@ -1470,6 +1470,17 @@ void launch_encode(const ScanDesc& proto, ScanDesc* d_descs, ScanResult* d_resul
             launch_encode_serial(d_descs + i, d_results + i, 1, stream);
 }
 
+bool launch_measure(const ScanDesc& proto, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count, hipStream_t stream)
+{
+    if (count == 0 || proto.restart_interval != 0)
+        return false;
+    const int lanes = group_encode_lanes(proto, count);
+    if (lanes == 0)
+        return false;
+    launch_measure_group(proto, lanes, d_descs, d_results, count, stream);
+    return true;
+}
+
 // Private stream buffers of the batch encoder's planar path (the component scans of a group of frames are coded into them
 // and then put in place): gigabytes, so they are kept between calls like the pipeline's work areas -- allocating and
 // freeing 8 GiB per call cost three times the coding of 256 4096 x 4096 RGB frames.

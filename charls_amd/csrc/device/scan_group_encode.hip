@@ -69,7 +69,10 @@ __host__ __device__ constexpr uint32_t encode_workgroup_lds_bytes(uint32_t width
 }
 
 // The reference's bit writer (src/scan_encoder.hpp:75-186) onto a staging ring; every member replicated over the lanes.
-struct RingWriter
+// kStore = false (the measuring form of the kernel): the bytes are formed and counted -- whether a byte is 0xFF decides the
+// width of the next one -- and stored nowhere.
+template <bool kStore>
+struct RingWriterT
 {
     uint8_t* ring;
     uint64_t remaining; // bytes of the destination not yet used
@@ -107,7 +110,8 @@ struct RingWriter
                 buf <<= 8;
                 free_bits += 8;
             }
-            ring[written & (kOutRingBytes - 1)] = (uint8_t)v;
+            if (kStore)
+                ring[written & (kOutRingBytes - 1)] = (uint8_t)v;
             ff = v == 0xFFu;
             --remaining;
             ++written;
@@ -184,6 +188,7 @@ struct RingWriter
         append((uint32_t)(m - 1) & ((1u << t.qbpp) - 1u), t.qbpp);
     }
 };
+using RingWriter = RingWriterT<true>;
 
 } // namespace grp
 
@@ -192,7 +197,11 @@ struct RingWriter
 // (src/scan_encoder_impl.hpp:109-160): the lines of a pixel row one component after the other, each against the line of
 // its own component above it and with its own RUNindex, on the one set of contexts; every component keeps its own pair
 // of lines, the user's row is de-interleaved into the NL current lines when its first component starts.
-template <typename S, int G, int NC, int NL = 1>
+// kMeasure: the MEASURING form.  The identical chain -- contexts, run mode, reconstruction, code words, the bit writer with
+// its 0xFF / 7-bit rule -- with nowhere to put the bytes: ScanDesc::stream, stream_capacity and line_scratch are not looked
+// at, nothing goes to the staging ring, destination_too_small is never raised, and ScanResult::bytes is the length of the
+// segment the encoding form writes for the same descriptor.
+template <typename S, int G, int NC, int NL = 1, bool kMeasure = false>
 __global__ void __launch_bounds__(64) encode_pixels_group(const ScanDesc* __restrict__ descs, ScanResult* __restrict__ results,
                                                           uint32_t count)
 {
@@ -242,9 +251,9 @@ __global__ void __launch_bounds__(64) encode_pixels_group(const ScanDesc* __rest
         for (uint32_t q = sub; q < 2 * NL * line_samples; q += G)
             line_a[q] = 0;
     }
-    RingWriter bw;
+    RingWriterT<!kMeasure> bw;
     bw.ring = out_ring;
-    bw.remaining = d.stream_capacity;
+    bw.remaining = kMeasure ? ~uint64_t{0} : d.stream_capacity;
     bw.written = 0;
     bw.buf = 0;
     bw.free_bits = 32;
@@ -434,7 +443,7 @@ __global__ void __launch_bounds__(64) encode_pixels_group(const ScanDesc* __rest
     {
         // ---- staging ring: drained before a burst of pixels could overrun it (a pixel writes at most NC * 8 + 8 bytes)
         {
-            const bool pending = phase != kDone && bw.written - copied >= kOutRingBytes / 2;
+            const bool pending = !kMeasure && phase != kDone && bw.written - copied >= kOutRingBytes / 2;
             if (__any(pending))
             {
                 JLS_LOCKSTEP();
@@ -773,7 +782,7 @@ __global__ void __launch_bounds__(64) encode_pixels_group(const ScanDesc* __rest
                 const bool todo = phase == kInLine && i <= width && bw.err == kOk;
                 general_pixel(todo);
                 if (__any(bw.err != kOk || (phase == kInLine && i > width) ||
-                          (phase != kDone && bw.written - copied >= kOutRingBytes / 2)))
+                          (!kMeasure && phase != kDone && bw.written - copied >= kOutRingBytes / 2)))
                     break;
             }
         }
@@ -819,9 +828,12 @@ __global__ void __launch_bounds__(64) encode_pixels_group(const ScanDesc* __rest
             {
                 if (finishing)
                     bw.end_scan();
-                JLS_LOCKSTEP();
-                drain(finishing && bw.err == kOk, true);
-                JLS_LOCKSTEP();
+                if (!kMeasure)
+                {
+                    JLS_LOCKSTEP();
+                    drain(finishing && bw.err == kOk, true);
+                    JLS_LOCKSTEP();
+                }
                 if (finishing)
                     phase = kDone;
             }

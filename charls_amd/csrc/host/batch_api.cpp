@@ -120,6 +120,30 @@ ScanDesc base_desc(const charls_frame_info& f, int32_t components, int32_t ilv, 
     return d;
 }
 
+// The container bytes in front of a frame's first scan, by the writer of part 1; returns their number.
+size_t write_prologue(const charls_amd_codec_params& p, const charls_jpegls_pc_parameters& pc, uint8_t* to, size_t capacity)
+{
+    const charls_frame_info& f = p.frame_info;
+    StreamWriter w;
+    w.set_destination(to, capacity);
+    w.start_of_image();
+    if (p.encoding_options & 2u)
+    {
+        static const char version[] = "charls 3.0.0";
+        w.comment(reinterpret_cast<const uint8_t*>(version), sizeof version);
+    }
+    if (p.color_transformation != 0)
+        w.color_transform(p.color_transformation);
+    if (w.start_of_frame(f))
+        w.oversize_dimensions(f.height, f.width);
+    if (!pc_is_default(p.preset_coding_parameters, default_pc(bit_max_value(f.bits_per_sample), p.near_lossless)) ||
+        ((p.encoding_options & 4u) && f.bits_per_sample > 12))
+        w.preset_coding_parameters(pc);
+    if (p.restart_interval != 0)
+        w.define_restart_interval(p.restart_interval);
+    return w.bytes_written();
+}
+
 thread_local bool t_force_rounds = false; // the batch encoder codes the component scans of planar frames one round per component
 
 } // namespace
@@ -129,6 +153,29 @@ void jls::check_encode_params(const charls_amd_codec_params& params, size_t fram
     size_t stride = 0;
     charls_jpegls_pc_parameters pc{};
     validate_encode(params, frame_bytes, stride_arg, &stride, &pc);
+}
+
+// What the encoder below does with `params` before it codes anything, for a caller that sizes streams without writing them
+// (batch_budget.cpp): the same validation, the scan descriptor without its pointers, the container bytes around the segments.
+EncodePlan jls::plan_encode(const charls_amd_codec_params& p, size_t frame_bytes, uint32_t stride_arg)
+{
+    EncodePlan plan{};
+    charls_jpegls_pc_parameters pc{};
+    validate_encode(p, frame_bytes, stride_arg, &plan.stride, &pc);
+    const charls_frame_info& f = p.frame_info;
+    plan.scans = p.interleave_mode == 0 ? static_cast<uint32_t>(f.component_count) : 1u;
+    const int32_t comps_per_scan = p.interleave_mode == 0 ? 1 : f.component_count;
+    plan.scan = base_desc(f, comps_per_scan, p.interleave_mode, p.near_lossless, p.color_transformation, pc, p.restart_interval);
+    plan.scan.pixel_stride = plan.stride;
+    uint8_t prologue[512];
+    plan.container_bytes = write_prologue(p, pc, prologue, sizeof prologue);
+    std::vector<uint8_t> tmp(static_cast<size_t>(plan.scans) * 16);
+    StreamWriter ws;
+    ws.set_destination(tmp.data(), tmp.size());
+    for (uint32_t r = 0; r < plan.scans; ++r)
+        ws.start_of_scan(comps_per_scan, p.near_lossless, p.interleave_mode);
+    plan.container_bytes += ws.bytes_written();
+    return plan;
 }
 
 // The batch encoder behind charls_amd_encode_batch_device (frames[i] = d_frames + i * frame_pitch_bytes) and
@@ -147,24 +194,7 @@ void jls::encode_batch_frames(const charls_amd_codec_params& p, uint32_t frame_c
 
     // ---- container bytes, produced once on the host by the writer of part 1
     uint8_t prologue[512];
-    StreamWriter w;
-    w.set_destination(prologue, sizeof prologue);
-    w.start_of_image();
-    if (p.encoding_options & 2u)
-    {
-        static const char version[] = "charls 3.0.0";
-        w.comment(reinterpret_cast<const uint8_t*>(version), sizeof version);
-    }
-    if (p.color_transformation != 0)
-        w.color_transform(p.color_transformation);
-    if (w.start_of_frame(f))
-        w.oversize_dimensions(f.height, f.width);
-    if (!pc_is_default(p.preset_coding_parameters, default_pc(bit_max_value(f.bits_per_sample), p.near_lossless)) ||
-        ((p.encoding_options & 4u) && f.bits_per_sample > 12))
-        w.preset_coding_parameters(pc);
-    if (p.restart_interval != 0)
-        w.define_restart_interval(p.restart_interval);
-    const uint32_t prologue_size = static_cast<uint32_t>(w.bytes_written());
+    const uint32_t prologue_size = static_cast<uint32_t>(write_prologue(p, pc, prologue, sizeof prologue));
 
     const uint32_t rounds = p.interleave_mode == 0 ? static_cast<uint32_t>(f.component_count) : 1u;
     const int32_t comps_per_scan = p.interleave_mode == 0 ? 1 : f.component_count;

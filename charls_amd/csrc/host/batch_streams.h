@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdint>
 
+#include "../device/scan_types.h"
 #include "common.h"
 
 namespace jls {
@@ -43,6 +44,16 @@ void encode_batch_frames(const charls_amd_codec_params& params, uint32_t frame_c
                          charls_jpegls_errc* errcs, void* hip_stream);
 // Raises what the batch encoder raises for these parameters before it codes anything (needs no GPU).
 void check_encode_params(const charls_amd_codec_params& params, size_t frame_bytes, uint32_t stride_arg);
+
+// What encode_batch_frames derives from `params` before it codes anything.  Raises what check_encode_params raises.
+struct EncodePlan
+{
+    size_t stride;            // bytes between rows
+    uint32_t scans;           // scans per frame: the components of a planar frame, else 1
+    ScanDesc scan;            // a scan of the frame without its pointers; scan r's pixels start r * stride * height into the frame
+    uint64_t container_bytes; // everything in front of the EOI marker that is no entropy-coded segment: prologue, SOS headers
+};
+EncodePlan plan_encode(const charls_amd_codec_params& params, size_t frame_bytes, uint32_t stride_arg);
 
 // charls_jpegls_encoder_get_estimated_destination_size for the frames of `p` (batch_packed.cpp).
 size_t estimated_stream_bytes(const charls_amd_codec_params& p);

@@ -637,6 +637,50 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_encode_batch_device_ragged(uint32_t
                                                                         uint32_t offset_alignment, uint64_t* offsets, uint64_t* sizes,
                                                                         charls_jpegls_errc* errcs, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Part 2f -- encoding to a BYTE BUDGET.  JPEG-LS has no rate control: the size of a frame at some NEAR is known only once
+ * it has been coded.  These calls walk the coding chains of every frame at every candidate NEAR in one launch that writes no
+ * stream (K candidates of N frames cost K x N x scans results of 16 bytes, no stream slots), report the sizes, and code
+ * every frame once, at the first candidate its budget allows.  Frames are uniform as in part 2 (frame f at d_frames +
+ * f * frame_pitch_bytes, one params, one stride); params->near_lossless is not looked at.  `near_candidates`, `budgets`,
+ * `sizes_out`, `offsets`, `sizes`, `near_out` and `errcs` are HOST arrays; candidate_count is 1 .. 64; the candidates may
+ * come in any order and may repeat: the order given is the order of preference.
+ *
+ * measure_batch_device: sizes_out[f * candidate_count + c] is the sizes[f] that charls_amd_encode_batch_device_packed
+ *   reports for frame f with near_lossless = near_candidates[c] and max_stream_bytes = 0 -- the complete .jls file, the
+ *   even-size padding included -- without writing any stream (0 for a frame the encoder fails on at that NEAR).
+ * encode_batch_device_budget: near_out[f] is the first candidate, in the order given, whose complete stream has at most
+ *   budgets[f] bytes -- a limit on the size of the result, not a destination capacity with the reference's four-bytes-spare
+ *   flush rule --, and frame f's bytes are exactly those charls_amd_encode_batch_device_packed produces with that
+ *   near_lossless and max_stream_bytes = 0.  No candidate fits: errcs[f] = destination_too_small, near_out[f] = -1,
+ *   sizes[f] = 0 and the frame takes no room.  Placement, offset_alignment, zeroed gaps and the capacity rule are those of
+ *   part 2d (offsets has frame_count + 1 elements): a frame whose end lies beyond packed_capacity_bytes is
+ *   destination_too_small (near_out[f] = -1), so is every frame after it, and nothing is written at or beyond the capacity.
+ * Errors of the whole call, checked before a device is asked for and before anything is written: NULL tables or pointers, a
+ *   candidate_count outside 1 .. 64, an offset_alignment that is no power of two in [1, 4096], and parameters the encoder
+ *   refuses with ANY of the candidates (the return value is the code for the first such candidate: NEAR above the largest
+ *   legal one, NEAR > 0 with a colour transformation, preset parameters invalid for that NEAR, ...).  frame_count == 0 is
+ *   success.
+ * How: the sizing launch is the group encoder's chain (contexts, run mode, reconstruction, Golomb code, bit writer with its
+ *   0xFF rule) without a destination, laid out candidate-major with as few lanes per chain as the count of chains allows;
+ *   the container bytes are added on the host.  The chosen (frame, NEAR) pairs are coded by
+ *   charls_amd_encode_batch_device_ragged -- frames of one NEAR are one group -- into staging slots sized by the largest
+ *   measured stream.  Scans the group encoder does not take (lines beyond LDS, charls_amd_set_encode_engine(1)) and frames
+ *   with a restart interval are sized by coding them for real into the staging work area, candidate by candidate in the
+ *   order given; the budget call stops at a frame's first candidate that fits, the measure call codes all of them.
+ * measure_counters: out[0] scans sized by the measuring kernels, out[1] launches of them, out[2] scans sized by coding them
+ *   for real; process-wide since load; returns the number of values written (3 at most).
+ * ---------------------------------------------------------------------------------------------------------------- */
+CHARLS_AMD_API charls_jpegls_errc charls_amd_measure_batch_device(const charls_amd_codec_params* params, uint32_t frame_count,
+                                                                  const void* d_frames, size_t frame_pitch_bytes, uint32_t stride,
+                                                                  const int32_t* near_candidates, uint32_t candidate_count,
+                                                                  uint64_t* sizes_out, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_encode_batch_device_budget(
+    const charls_amd_codec_params* params, uint32_t frame_count, const void* d_frames, size_t frame_pitch_bytes, uint32_t stride,
+    const uint64_t* budgets, const int32_t* near_candidates, uint32_t candidate_count, void* d_packed, size_t packed_capacity_bytes,
+    uint32_t offset_alignment, uint64_t* offsets, uint64_t* sizes, int32_t* near_out, charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API int32_t charls_amd_measure_counters(uint64_t* out, int32_t capacity);
+
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */
 CHARLS_AMD_API charls_jpegls_errc charls_amd_set_encode_engine(int32_t engine);
