@@ -101,7 +101,22 @@ typedef struct
     uint64_t rcache;
     int rvalid;
     uint32_t rst_counter;
+    /* event counters (jls_oracle.h, JLS_CENSUS_*); NULL for every entry point but the *_census ones */
+    uint64_t* census;
 } codec;
+
+#define CENSUS(c, id) \
+    do \
+    { \
+        if ((c)->census) \
+            ++(c)->census[id]; \
+    } while (0)
+#define CENSUS_MAX(c, id, v) \
+    do \
+    { \
+        if ((c)->census && (c)->census[id] < (uint64_t)(v)) \
+            (c)->census[id] = (uint64_t)(v); \
+    } while (0)
 
 static void fail(codec* c, int errc)
 {
@@ -247,6 +262,15 @@ static int32_t correct_prediction(const codec* c, int32_t p) /* src/default_trai
     return p;
 }
 
+static int32_t corrected_prediction(const codec* c, int32_t p) /* correct_prediction of Px + C, counted */
+{
+    if (p < 0)
+        CENSUS(c, JLS_CENSUS_PREDICTION_CLAMP_LOW);
+    else if (p > c->maxval)
+        CENSUS(c, JLS_CENSUS_PREDICTION_CLAMP_HIGH);
+    return correct_prediction(c, p);
+}
+
 static int32_t compute_error_value(const codec* c, int32_t e) /* src/default_traits.hpp:77-80,123-139,157-163 */
 {
     const int32_t d = 2 * c->near + 1;
@@ -262,9 +286,15 @@ static int32_t reconstruct(const codec* c, int32_t predicted, int32_t e) /* src/
 {
     int32_t v = predicted + e * (2 * c->near + 1);
     if (v < -c->near)
+    {
+        CENSUS(c, JLS_CENSUS_WRAP_LOW);
         v += c->range * (2 * c->near + 1);
+    }
     else if (v > c->maxval + c->near)
+    {
+        CENSUS(c, JLS_CENSUS_WRAP_HIGH);
         v -= c->range * (2 * c->near + 1);
+    }
     return correct_prediction(c, v);
 }
 
@@ -303,6 +333,9 @@ static int reg_k(codec* c, const reg_ctx* x) /* src/regular_mode_context.hpp:99-
         ++k;
     if (k == 16)
         fail(c, E_INVALID_DATA);
+    CENSUS_MAX(c, JLS_CENSUS_MAX_REGULAR_K, k);
+    if ((x->n << k) == x->a)
+        CENSUS(c, JLS_CENSUS_N_SHL_K_EQ_A);
     return k;
 }
 
@@ -314,6 +347,7 @@ static void reg_update(codec* c, reg_ctx* x, int32_t e) /* src/regular_mode_cont
         fail(c, E_INVALID_DATA);
     if (x->n == c->reset)
     {
+        CENSUS(c, JLS_CENSUS_REGULAR_HALVED);
         x->a >>= 1;
         x->b >>= 1; /* arithmetic shift of a possibly negative value, as the reference relies on */
         x->n >>= 1;
@@ -323,17 +357,27 @@ static void reg_update(codec* c, reg_ctx* x, int32_t e) /* src/regular_mode_cont
     {
         x->b += x->n;
         if (x->b <= -x->n)
+        {
+            CENSUS(c, JLS_CENSUS_B_CLAMP_LOW);
             x->b = -x->n + 1;
+        }
         if (x->c > -128)
             --x->c;
+        else
+            CENSUS(c, JLS_CENSUS_C_CLAMP_LOW);
     }
     else if (x->b > 0)
     {
         x->b -= x->n;
         if (x->b > 0)
+        {
+            CENSUS(c, JLS_CENSUS_B_CLAMP_HIGH);
             x->b = 0;
+        }
         if (x->c < 127)
             ++x->c;
+        else
+            CENSUS(c, JLS_CENSUS_C_CLAMP_HIGH);
     }
 }
 
@@ -352,6 +396,7 @@ static int run_k(codec* c, const run_ctx* x, int checked) /* src/run_mode_contex
             break;
         }
     }
+    CENSUS_MAX(c, JLS_CENSUS_MAX_RUN_K, k);
     return k;
 }
 
@@ -373,6 +418,7 @@ static void run_update(codec* c, run_ctx* x, int32_t e, int32_t em) /* src/run_m
     x->a += (em + 1 - x->ritype) >> 1;
     if (x->n == c->reset)
     {
+        CENSUS(c, JLS_CENSUS_RUN_HALVED);
         x->a >>= 1;
         x->n >>= 1;
         x->nn >>= 1;
@@ -458,9 +504,22 @@ static void w_end_scan(codec* c) /* src/scan_encoder.hpp:103-115 */
     w_flush(c);
 }
 
-static void encode_mapped(codec* c, int k, int32_t m, int limit) /* src/scan_encoder_core.hpp:69-103 */
+/* Census of one Golomb code: `zeros` zero bits, the 1, then `tail` bits (k, or qbpp for an escape code). */
+static void census_code(codec* c, int32_t zeros, int tail, int escape, int ri)
+{
+    if (escape)
+        CENSUS(c, ri ? JLS_CENSUS_ESCAPE_RUN : JLS_CENSUS_ESCAPE_REGULAR);
+    if (zeros + 1 > 31)
+        CENSUS(c, JLS_CENSUS_PREFIX_OVER_31);
+    if (zeros + 1 + tail >= 32)
+        CENSUS(c, JLS_CENSUS_CODE_32_OR_MORE);
+}
+
+static void encode_mapped(codec* c, int k, int32_t m, int limit, int ri) /* src/scan_encoder_core.hpp:69-103 */
 {
     int32_t hb = m >> k;
+    census_code(c, hb < limit - c->qbpp - 1 ? hb : limit - c->qbpp - 1, hb < limit - c->qbpp - 1 ? k : c->qbpp,
+                !(hb < limit - c->qbpp - 1), ri);
     if (hb < limit - c->qbpp - 1)
     {
         if (hb + 1 > 31)
@@ -601,11 +660,15 @@ static int32_t r_unary(codec* c) /* src/scan_decoder.hpp:176-217 */
             return zeros;
 }
 
-static int32_t decode_mapped(codec* c, int k, int limit) /* src/scan_decoder.hpp:113-125 */
+static int32_t decode_mapped(codec* c, int k, int limit, int ri) /* src/scan_decoder.hpp:113-125 */
 {
     const int32_t u = r_unary(c);
     if (u < limit - c->qbpp - 1)
+    {
+        census_code(c, u, k, 0, ri);
         return k == 0 ? u : (u << k) + r_value(c, k);
+    }
+    census_code(c, u, c->qbpp, 1, ri);
     return r_value(c, c->qbpp) + 1;
 }
 
@@ -676,12 +739,14 @@ static int32_t encode_regular(codec* c, int32_t qs, int32_t x, int32_t pred) /* 
     const int32_t s = qs < 0 ? -1 : 0;
     reg_ctx* ctx = &c->reg[(qs ^ s) - s];
     const int k = reg_k(c, ctx);
-    const int32_t px = correct_prediction(c, pred + ((ctx->c ^ s) - s));
+    const int32_t px = corrected_prediction(c, pred + ((ctx->c ^ s) - s));
     const int32_t e = compute_error_value(c, ((x - px) ^ s) - s);
     int32_t corr = 0;
     if ((k | c->near) == 0)
         corr = (2 * ctx->b + ctx->n - 1) < 0 ? -1 : 0; /* src/regular_mode_context.hpp:36-42 */
-    encode_mapped(c, k, jls_oracle_map_error(corr ^ e), c->limit);
+    if (corr)
+        CENSUS(c, JLS_CENSUS_ERROR_CORRECTION);
+    encode_mapped(c, k, jls_oracle_map_error(corr ^ e), c->limit, 0);
     reg_update(c, ctx, e);
     return reconstruct(c, px, (e ^ s) - s);
 }
@@ -690,7 +755,7 @@ static int32_t decode_regular(codec* c, int32_t qs, int32_t pred) /* src/scan_de
 {
     const int32_t s = qs < 0 ? -1 : 0;
     reg_ctx* ctx = &c->reg[(qs ^ s) - s];
-    const int32_t px = correct_prediction(c, pred + ((ctx->c ^ s) - s));
+    const int32_t px = corrected_prediction(c, pred + ((ctx->c ^ s) - s));
     const int k = reg_k(c, ctx);
     int32_t e;
     const unsigned top = r_peek_byte(c);
@@ -705,12 +770,15 @@ static int32_t decode_regular(codec* c, int32_t qs, int32_t pred) /* src/scan_de
     }
     else
     {
-        e = jls_oracle_unmap_error(decode_mapped(c, k, c->limit));
+        e = jls_oracle_unmap_error(decode_mapped(c, k, c->limit, 0));
         if (e > 65535 || e < -65535)
             fail(c, E_INVALID_DATA);
     }
-    if (k == 0 && c->near == 0)
-        e ^= (2 * ctx->b + ctx->n - 1) < 0 ? -1 : 0;
+    if (k == 0 && c->near == 0 && (2 * ctx->b + ctx->n - 1) < 0)
+    {
+        CENSUS(c, JLS_CENSUS_ERROR_CORRECTION);
+        e ^= -1;
+    }
     reg_update(c, ctx, e);
     return reconstruct(c, px, (e ^ s) - s);
 }
@@ -720,14 +788,20 @@ static void encode_ri_error(codec* c, run_ctx* ctx, int32_t e) /* src/scan_encod
     const int k = run_k(c, ctx, 0);
     const int map = run_map(ctx, e, k);
     const int32_t em = 2 * (e < 0 ? -e : e) - ctx->ritype - map;
-    encode_mapped(c, k, em, c->limit - J[c->run_index] - 1);
+    CENSUS(c, ctx->ritype ? JLS_CENSUS_RITYPE_1 : JLS_CENSUS_RITYPE_0);
+    if (map)
+        CENSUS(c, JLS_CENSUS_MAP_1);
+    encode_mapped(c, k, em, c->limit - J[c->run_index] - 1, 1);
     run_update(c, ctx, e, em);
 }
 
 static int32_t decode_ri_error(codec* c, run_ctx* ctx) /* src/scan_decoder_core.hpp:72-81 */
 {
     const int k = run_k(c, ctx, 1);
-    const int32_t em = decode_mapped(c, k, c->limit - J[c->run_index] - 1);
+    const int32_t em = decode_mapped(c, k, c->limit - J[c->run_index] - 1, 1);
+    CENSUS(c, ctx->ritype ? JLS_CENSUS_RITYPE_1 : JLS_CENSUS_RITYPE_0);
+    if ((em + ctx->ritype) & 1)
+        CENSUS(c, JLS_CENSUS_MAP_1);
     const int32_t e = run_error_value(ctx, em + ctx->ritype, k);
     run_update(c, ctx, e, em);
     return e;
@@ -741,11 +815,17 @@ static void encode_run_pixels(codec* c, size_t run_length, int eol) /* src/scan_
         run_length -= (size_t)1 << J[c->run_index];
         if (c->run_index < 31)
             ++c->run_index;
+        else
+            CENSUS(c, JLS_CENSUS_BLOCK_AT_RUN_INDEX_31);
+        CENSUS_MAX(c, JLS_CENSUS_MAX_RUN_INDEX, c->run_index);
     }
     if (eol)
     {
         if (run_length != 0)
+        {
+            CENSUS(c, JLS_CENSUS_PARTIAL_BLOCK_AT_LINE_END);
             w_append(c, 1, 1);
+        }
     }
     else
         w_append(c, (uint32_t)run_length, J[c->run_index] + 1);
@@ -759,8 +839,13 @@ static size_t decode_run_pixels(codec* c, size_t remaining) /* src/scan_decoder_
         const size_t block = (size_t)1 << J[c->run_index];
         const size_t count = block < remaining - index ? block : remaining - index;
         index += count;
+        if (count != block)
+            CENSUS(c, JLS_CENSUS_PARTIAL_BLOCK_AT_LINE_END);
+        else if (c->run_index == 31)
+            CENSUS(c, JLS_CENSUS_BLOCK_AT_RUN_INDEX_31);
         if (count == block && c->run_index < 31)
             ++c->run_index;
+        CENSUS_MAX(c, JLS_CENSUS_MAX_RUN_INDEX, c->run_index);
         if (index == remaining)
             break;
     }
@@ -1145,8 +1230,8 @@ static void decode_lines(codec* c, uint8_t* dst, size_t stride_bytes)
     }
 }
 
-int jls_oracle_encode_scan(const jls_oracle_params* params, const void* source, size_t stride, void* destination,
-                           size_t destination_size, size_t* bytes_written)
+static int encode_scan(const jls_oracle_params* params, const void* source, size_t stride, void* destination,
+                       size_t destination_size, size_t* bytes_written, uint64_t* census)
 {
     codec* c = malloc(sizeof *c);
     if (!c)
@@ -1154,6 +1239,7 @@ int jls_oracle_encode_scan(const jls_oracle_params* params, const void* source, 
     int rc = scan_setup(c, params);
     if (rc == E_OK)
     {
+        c->census = census;
         rc = setjmp(c->fail);
         if (rc == 0)
         {
@@ -1168,8 +1254,14 @@ int jls_oracle_encode_scan(const jls_oracle_params* params, const void* source, 
     return rc;
 }
 
-int jls_oracle_decode_scan(const jls_oracle_params* params, const void* source, size_t source_size, void* destination,
-                           size_t stride, size_t* bytes_read)
+int jls_oracle_encode_scan(const jls_oracle_params* params, const void* source, size_t stride, void* destination,
+                           size_t destination_size, size_t* bytes_written)
+{
+    return encode_scan(params, source, stride, destination, destination_size, bytes_written, NULL);
+}
+
+static int decode_scan(const jls_oracle_params* params, const void* source, size_t source_size, void* destination,
+                       size_t stride, size_t* bytes_read, uint64_t* census)
 {
     codec* c = malloc(sizeof *c);
     if (!c)
@@ -1177,6 +1269,7 @@ int jls_oracle_decode_scan(const jls_oracle_params* params, const void* source, 
     int rc = scan_setup(c, params);
     if (rc == E_OK)
     {
+        c->census = census;
         rc = setjmp(c->fail);
         if (rc == 0)
         {
@@ -1189,6 +1282,12 @@ int jls_oracle_decode_scan(const jls_oracle_params* params, const void* source, 
     scan_free(c);
     free(c);
     return rc;
+}
+
+int jls_oracle_decode_scan(const jls_oracle_params* params, const void* source, size_t source_size, void* destination,
+                           size_t stride, size_t* bytes_read)
+{
+    return decode_scan(params, source, source_size, destination, stride, bytes_read, NULL);
 }
 
 int jls_oracle_bitwriter_kat(const uint32_t* values, const int32_t* bit_counts, int count, uint8_t* destination,
@@ -1263,8 +1362,8 @@ static int color_transform_possible(const jls_oracle_params* p) /* src/color_tra
            p->interleave_mode != 0;
 }
 
-int jls_oracle_encode(const jls_oracle_params* p, const void* source, size_t source_size, uint32_t stride_arg,
-                      void* destination, size_t destination_size, size_t* bytes_written)
+static int encode_file(const jls_oracle_params* p, const void* source, size_t source_size, uint32_t stride_arg,
+                       void* destination, size_t destination_size, size_t* bytes_written, uint64_t* census)
 { /* src/charls_jpegls_encoder.cpp:44-53,182-236,285-424 */
     if (!source || !destination || !bytes_written)
         return E_INVALID_ARGUMENT;
@@ -1400,7 +1499,7 @@ int jls_oracle_encode(const jls_oracle_params* p, const void* source, size_t sou
         wr_u8(&w, 0);
         sp.component_count = comps_per_scan;
         size_t n = 0;
-        const int rc = jls_oracle_encode_scan(&sp, src, stride, w.p + w.off, w.cap - w.off, &n);
+        const int rc = encode_scan(&sp, src, stride, w.p + w.off, w.cap - w.off, &n, census);
         if (rc != E_OK)
             return rc;
         w.off += n;
@@ -1416,6 +1515,22 @@ int jls_oracle_encode(const jls_oracle_params* p, const void* source, size_t sou
         return w.err;
     *bytes_written = w.off;
     return E_OK;
+}
+
+int jls_oracle_encode(const jls_oracle_params* p, const void* source, size_t source_size, uint32_t stride,
+                      void* destination, size_t destination_size, size_t* bytes_written)
+{
+    return encode_file(p, source, source_size, stride, destination, destination_size, bytes_written, NULL);
+}
+
+int jls_oracle_encode_census(const jls_oracle_params* p, const void* source, size_t source_size, uint32_t stride,
+                             void* destination, size_t destination_size, size_t* bytes_written,
+                             uint64_t counts[JLS_CENSUS_COUNT])
+{
+    if (!counts)
+        return E_INVALID_ARGUMENT;
+    memset(counts, 0, JLS_CENSUS_COUNT * sizeof counts[0]);
+    return encode_file(p, source, source_size, stride, destination, destination_size, bytes_written, counts);
 }
 
 /* ---------------------------------------------------------------- container: reader (subset of src/jpeg_stream_reader.cpp) */
@@ -1655,8 +1770,8 @@ int jls_oracle_read_header(const void* source, size_t source_size, jls_oracle_pa
     return rc;
 }
 
-int jls_oracle_decode(const void* source, size_t source_size, void* destination, size_t destination_size,
-                      uint32_t stride_arg, jls_oracle_params* params_out)
+static int decode_file(const void* source, size_t source_size, void* destination, size_t destination_size,
+                       uint32_t stride_arg, jls_oracle_params* params_out, uint64_t* census)
 { /* src/charls_jpegls_decoder.cpp:177-247 */
     rd r;
     int rc = rd_header(&r, source, source_size);
@@ -1689,7 +1804,7 @@ int jls_oracle_decode(const void* source, size_t source_size, void* destination,
         sp.threshold3 = pc[3];
         sp.reset_value = pc[4];
         size_t used = 0;
-        rc = jls_oracle_decode_scan(&sp, r.p, (size_t)(r.end - r.p), dst, stride, &used);
+        rc = decode_scan(&sp, r.p, (size_t)(r.end - r.p), dst, stride, &used, census);
         if (rc)
             return rc;
         r.p += used;
@@ -1726,4 +1841,19 @@ int jls_oracle_decode(const void* source, size_t source_size, void* destination,
     if (params_out)
         *params_out = r.prm;
     return E_OK;
+}
+
+int jls_oracle_decode(const void* source, size_t source_size, void* destination, size_t destination_size,
+                      uint32_t stride, jls_oracle_params* params_out)
+{
+    return decode_file(source, source_size, destination, destination_size, stride, params_out, NULL);
+}
+
+int jls_oracle_decode_census(const void* source, size_t source_size, void* destination, size_t destination_size,
+                             uint32_t stride, jls_oracle_params* params_out, uint64_t counts[JLS_CENSUS_COUNT])
+{
+    if (!counts)
+        return E_INVALID_ARGUMENT;
+    memset(counts, 0, JLS_CENSUS_COUNT * sizeof counts[0]);
+    return decode_file(source, source_size, destination, destination_size, stride, params_out, counts);
 }

@@ -21,6 +21,14 @@ class Params(C.Structure):
                 ("encoding_options", C.c_uint32), ("restart_interval", C.c_uint32)]
 
 
+# enum jls_census of oracle/jls_oracle.h, in its order
+CENSUS = ("c_clamp_low", "c_clamp_high", "b_clamp_low", "b_clamp_high", "regular_halved", "run_halved", "max_regular_k",
+          "max_run_k", "n_shl_k_eq_a", "error_correction", "escape_regular", "escape_run", "prefix_over_31",
+          "code_32_or_more", "wrap_low", "wrap_high", "prediction_clamp_low", "prediction_clamp_high", "ritype_0",
+          "ritype_1", "map_1", "max_run_index", "block_at_run_index_31", "partial_block_at_line_end")
+CENSUS_MAXIMA = ("max_regular_k", "max_run_k", "max_run_index")  # the largest value seen; every other entry counts events
+
+
 class OracleError(RuntimeError):
     def __init__(self, errc):
         self.errc = int(errc)
@@ -44,12 +52,16 @@ def lib():
         L.jls_oracle_default_pc.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
         L.jls_oracle_bitwriter_kat.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_int, C.c_void_p,
                                                C.c_size_t, C.POINTER(C.c_size_t)]
+        counts = C.POINTER(C.c_uint64 * len(CENSUS))
+        L.jls_oracle_encode_census.argtypes = L.jls_oracle_encode.argtypes + [counts]
+        L.jls_oracle_decode_census.argtypes = L.jls_oracle_decode.argtypes + [counts]
         _lib = L
     return _lib
 
 
 def encode(image, *, width, height, bits_per_sample=8, component_count=1, near_lossless=0, interleave_mode=0,
-           color_transformation=0, preset=None, encoding_options=0, stride=0, destination_size=None) -> bytes:
+           color_transformation=0, preset=None, encoding_options=0, stride=0, destination_size=None, census=None) -> bytes:
+    """`census`: a dict that receives the event counters of jls_oracle_encode_census, by the names of CENSUS."""
     a = np.ascontiguousarray(image) if isinstance(image, np.ndarray) else np.frombuffer(bytes(image), dtype=np.uint8)
     pc = preset or (0, 0, 0, 0, 0)
     p = Params(width, height, bits_per_sample, component_count, near_lossless, interleave_mode, color_transformation,
@@ -59,7 +71,13 @@ def encode(image, *, width, height, bits_per_sample=8, component_count=1, near_l
         destination_size = raw + raw // 16 + 1024 + 34
     dst = np.empty(destination_size, dtype=np.uint8)
     n = C.c_size_t()
-    rc = lib().jls_oracle_encode(C.byref(p), a.ctypes.data, a.nbytes, stride, dst.ctypes.data, dst.nbytes, C.byref(n))
+    if census is None:
+        rc = lib().jls_oracle_encode(C.byref(p), a.ctypes.data, a.nbytes, stride, dst.ctypes.data, dst.nbytes, C.byref(n))
+    else:
+        counts = (C.c_uint64 * len(CENSUS))()
+        rc = lib().jls_oracle_encode_census(C.byref(p), a.ctypes.data, a.nbytes, stride, dst.ctypes.data, dst.nbytes,
+                                            C.byref(n), C.byref(counts))
+        census.update(zip(CENSUS, (int(v) for v in counts)))
     if rc:
         raise OracleError(rc)
     return dst[:n.value].tobytes()
@@ -74,7 +92,7 @@ def read_header(data) -> Params:
     return p
 
 
-def decode(data, stride=0):
+def decode(data, stride=0, census=None):
     b = np.frombuffer(bytes(data), dtype=np.uint8)
     p = read_header(data)
     bytes_ps = (p.bits_per_sample + 7) // 8
@@ -86,7 +104,13 @@ def decode(data, stride=0):
         size = stride * p.height
     out = np.zeros(size, dtype=np.uint8)
     q = Params()
-    rc = lib().jls_oracle_decode(b.ctypes.data, b.nbytes, out.ctypes.data, out.nbytes, stride, C.byref(q))
+    if census is None:
+        rc = lib().jls_oracle_decode(b.ctypes.data, b.nbytes, out.ctypes.data, out.nbytes, stride, C.byref(q))
+    else:
+        counts = (C.c_uint64 * len(CENSUS))()
+        rc = lib().jls_oracle_decode_census(b.ctypes.data, b.nbytes, out.ctypes.data, out.nbytes, stride, C.byref(q),
+                                            C.byref(counts))
+        census.update(zip(CENSUS, (int(v) for v in counts)))
     if rc:
         raise OracleError(rc)
     return q, out

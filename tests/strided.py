@@ -179,8 +179,10 @@ def mixed(g: Geometry, seed, kind="mixed"):
 class Coded:
     """A packed frame, the oracle's stream of it and the oracle's pixels of that stream."""
 
-    def __init__(self, g: Geometry, seed, *, near=0, ct=0, preset=None, kind="mixed", restart=0, product=None):
-        self.g, self.img = g, mixed(g, seed, kind)
+    def __init__(self, g: Geometry, seed, *, near=0, ct=0, preset=None, kind="mixed", restart=0, product=None, img=None):
+        """`img`: given pixels in the user's layout (tests/corners.py) instead of the frame `seed` and `kind` make."""
+        self.g, self.img = g, mixed(g, seed, kind) if img is None else np.ascontiguousarray(img)
+        assert self.img.nbytes == g.packed, (self.img.nbytes, g.packed)
         kw = dict(near_lossless=near, color_transformation=ct, preset=preset, destination_size=8 * g.packed + 4096, **g.kw())
         # a stream with restart markers is the product encoder's extension (the reference cannot write one): written from
         # the PACKED image, and what it holds is what the oracle decodes from it
