@@ -89,7 +89,6 @@ constexpr uint32_t run_slots_of()
 {
     return sizeof(Slot<S>) == 2 ? 2u : 1u;
 }
-constexpr uint32_t kRowChainWords = 288;    // LDS words of the sort stage's row table: a tile has at most (12288 + 16) / 64 + 367 rows of 64 slots (2 bytes each)
 constexpr uint32_t kChainPad = 32;         // chains start on multiples of 32 slots (64 or 128 bytes: whole lines)
 constexpr uint32_t kSlack = kChains * kChainPad + 128; // spare slots behind rec / code: padding + read-ahead of the walkers
 // Slots the chains of `samples` samples in `lines` lines can take at most: every sample has at most one event, a run start
@@ -340,6 +339,121 @@ JLS_DEV void block_exclusive_scan_pair(uint32_t (&a)[2], uint32_t (&b)[2], uint3
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The piece copies (P3 of sort_tiles / sort_pixel_tiles, the code-word phase of pack_tiles).  A tile's local order in LDS is
+// "chains in order, each chain's piece contiguous", so moving it to or from the chain-ordered global arrays is ONE flat copy
+// with a piecewise-constant address offset: local slot t of piece k lies at global slot t + delta[k].  A wavefront takes FLAT
+// rows -- row r is local slots 64 r ... 64 r + 63, whatever pieces they belong to -- and a lane finds its piece without a
+// search, from two small tables:
+//   pieces  the non-empty pieces, numbered k = 0, 1, ... in chain order: delta[k] = global start - local start (mod 2^32),
+//           and behind them kPieceInfo words about the tile (PieceInfo)
+//   rows    16 bytes per flat row: x = the piece that holds slot 64 r, (z, w) = a 64-bit mask whose bit j - 1 is set when a
+//           piece starts at slot 64 r + j (j = 1 ... 63).  The lane's piece is x + the set bits below its own.
+// The chain's thread adds its piece (piece_tables_add): one delta, one start bit ORed into its row, and x of the rows whose
+// first slot lies inside the piece -- about slots / 64 + pieces stores per tile.  (Until round 14 the copies ran one 64-lane
+// row PER CHAIN PIECE: ~230 rows for 128 rows' worth of slots on a bench tile, five dependent table reads per row.)
+constexpr uint32_t kPieceRows = (kMaxTileSamples + kMaxTileSamples / 2 + kTileLines + 63) / 64; // flat rows of a tile at most (slots_capacity of a full tile of 2-byte slots: 12288 + 16)
+constexpr uint32_t kPieceInfo = 4;
+constexpr uint32_t kPieceWords = kChains + kPieceInfo;  // LDS words of the piece table
+constexpr uint32_t kNoPiece = 0xFFFFFFFFu;
+enum PieceInfo : uint32_t
+{
+    kPieceTotal = 0, // local slots of the tile
+    kPieceSkip = 1,  // the piece whose slots the copy leaves out (sort_tiles: the interruption chain has no records), or kNoPiece
+    kPieceRun = 2    // slots of chain 0 (pack_tiles: the run chain's entries take two 2-byte slots)
+};
+// Before the barrier(s) that piece_tables_add is behind: all threads of the workgroup.
+JLS_DEV void piece_tables_clear(uint4* rows, uint32_t* pieces)
+{
+    for (uint32_t r = threadIdx.x; r < kPieceRows; r += blockDim.x)
+        rows[r] = make_uint4(0, 0, 0, 0);
+    if (threadIdx.x < kPieceInfo)
+        pieces[kChains + threadIdx.x] = threadIdx.x == kPieceSkip ? kNoPiece : 0u;
+}
+// The thread of a chain whose piece has n > 0 slots from local slot `off`, k non-empty pieces before it, global start `global`.
+JLS_DEV void piece_tables_add(uint4* rows, uint32_t* pieces, uint32_t k, uint32_t off, uint32_t n, uint32_t global)
+{
+    uint32_t* words = reinterpret_cast<uint32_t*>(rows);
+    pieces[k] = global - off;
+    const uint32_t j = off & 63u;
+    if (j != 0)
+        atomicOr(&words[(off >> 6) * 4 + 2 + ((j - 1) >> 5)], 1u << ((j - 1) & 31u));
+    for (uint32_t r = (off + 63) >> 6; r * 64 < off + n; ++r)
+        words[r * 4] = k;
+}
+// The piece of this lane's slot in the flat row with entry e (wave-uniform): two v_mbcnt.
+JLS_DEV uint32_t piece_of_lane(const uint4& e, int lane)
+{
+#ifdef JLS_EMULATED
+    const unsigned long long starts = (unsigned long long)e.z | ((unsigned long long)e.w << 32);
+    return e.x + (uint32_t)__popcll(starts & ((1ull << lane) - 1ull));
+#else
+    (void)lane;
+    return e.x + __builtin_amdgcn_mbcnt_hi(e.w, __builtin_amdgcn_mbcnt_lo(e.z, 0u));
+#endif
+}
+// Pieces out of LDS (the sort kernels): `from` = the tile's slots in local order.  kRows flat rows at a time.  Nothing but
+// the store itself stands under a condition: a row behind the tile's last one is that last row again and a lane behind the
+// tile's last slot takes that slot, so the table reads and the slot reads of a batch are issued back to back (under the
+// condition they came out as one branch per row with two LDS waits inside).  All threads of the workgroup, behind the
+// barrier that follows the last piece_tables_add.
+template <typename T, int kRows>
+JLS_DEV void copy_pieces_out(const uint4* rows, const uint32_t* pieces, const T* from, JLS_GLOBAL_AS T* to, uint32_t waves)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t total = pieces[kChains + kPieceTotal], skip = pieces[kChains + kPieceSkip];
+    const uint32_t total_rows = (total + 63) / 64;
+    for (uint32_t q0 = (uint32_t)wave * kRows; q0 < total_rows; q0 += waves * kRows)
+    {
+        uint32_t at[kRows];
+        T held[kRows];
+        bool live[kRows];
+#pragma unroll
+        for (int j = 0; j < kRows; ++j)
+        {
+            const uint32_t q = q0 + (uint32_t)j < total_rows ? q0 + (uint32_t)j : total_rows - 1; // (uniform)
+            const uint32_t t = q * 64 + (uint32_t)lane;
+            const uint32_t k = piece_of_lane(rows[q], lane); // (no piece starts behind the tile's last slot)
+            const uint32_t tc = t < total ? t : total - 1;
+            live[j] = q0 + (uint32_t)j < total_rows && t < total && k != skip;
+            at[j] = tc + pieces[k];
+            held[j] = from[tc];
+        }
+#pragma unroll
+        for (int j = 0; j < kRows; ++j)
+            if (live[j])
+                to[at[j]] = held[j];
+    }
+}
+// Pieces into LDS (pack_tiles): every slot of the tile, kRows flat rows requested together.  Every lane loads, from a slot of
+// the tile (see above), and only the store into LDS stands under a condition.
+template <typename T, int kRows>
+JLS_DEV void copy_pieces_in(const uint4* rows, const uint32_t* pieces, const JLS_GLOBAL_AS T* from, T* to, uint32_t waves)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t total = pieces[kChains + kPieceTotal];
+    const uint32_t total_rows = (total + 63) / 64;
+    for (uint32_t q0 = (uint32_t)wave * kRows; q0 < total_rows; q0 += waves * kRows)
+    {
+        T held[kRows];
+#pragma unroll
+        for (int j = 0; j < kRows; ++j)
+        {
+            const uint32_t q = q0 + (uint32_t)j < total_rows ? q0 + (uint32_t)j : total_rows - 1; // (uniform)
+            const uint32_t t = q * 64 + (uint32_t)lane;
+            const uint32_t k = piece_of_lane(rows[q], lane);
+            held[j] = from[(t < total ? t : total - 1) + pieces[k]];
+        }
+#pragma unroll
+        for (int j = 0; j < kRows; ++j)
+        {
+            const uint32_t t = (q0 + (uint32_t)j) * 64 + (uint32_t)lane;
+            if (t < total)
+                to[t] = held[j];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // The lines of a tile and the line above it, staged in LDS (planar scans): analysis reads every sample five times (x, Ra,
 // Rb, Rc, Rd); out of LDS those reads cost an LDS latency instead of a trip to the L2, and the staging itself is wide
 // coalesced loads issued back to back.  (analyze_tiles / sort_tiles are the specialisation for PLANAR scans whose lines fit
@@ -466,13 +580,16 @@ __global__ void __launch_bounds__(kThreads) analyze_tiles(const ScanDesc* __rest
     const int mask = (1 << d.bits_per_sample) - 1;
     const Samples<S, ILV> sample{d, s_rows, g.first_line, mask};
 
+    JLS_PHASE_BEGIN();
     stage_lines<S, ILV>(d, g, s_rows);
+    JLS_PHASE(22);
     for (uint32_t c = threadIdx.x; c < (uint32_t)kChains; c += kThreads)
         s_hist[c] = 0;
     if (sizeof(S) == 1)
         for (uint32_t q = threadIdx.x; q < 511; q += kThreads)
             s_grad[q] = (unsigned char)(quantize(t, (int)q - 255) + 4);
     __syncthreads();
+    JLS_PHASE(23);
 
     // ---- pass 1: every sample as if coded in regular mode; equality / zero-context masks per 64-sample chunk
     for (uint32_t sgm = wave; sgm < g.segments; sgm += kWaves)
@@ -519,7 +636,9 @@ __global__ void __launch_bounds__(kThreads) analyze_tiles(const ScanDesc* __rest
             }
         }
     }
+    JLS_PHASE(24);
     __syncthreads();
+    JLS_PHASE(25);
     // ---- pass 2: run-mode state before every sample.  s' = eq & (s | q0) is a carry chain: generate = eq & q0,
     // propagate = eq, so one 64-bit addition per chunk resolves 64 samples (src/scan_encoder_impl.hpp:249-275).  A piece
     // that does not start its line first runs the (scalar) chain over the chunks before it.
@@ -563,9 +682,11 @@ __global__ void __launch_bounds__(kThreads) analyze_tiles(const ScanDesc* __rest
             }
         }
     }
+    JLS_PHASE(26);
     __syncthreads();
     for (uint32_t c = threadIdx.x; c < (uint32_t)kChains; c += kThreads)
         global_ptr(w.seg)[(size_t)tile * kChains + c] = s_hist[c];
+    JLS_PHASE(27);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -724,8 +845,8 @@ struct RunRecord
 };
 
 // B2: grid (8 * ceil(tiles / 8), scans) x 512.
-// LDS: lines | keys[tile] u16 | noev[line][chunk] u64, lead[line][chunk + 1] u32 | segoff[kSegments][kChains] u32 |
-//      tileoff, count, global [kChains + 1] | scan scratch | same[kWaves][kChains + 1] | stage[tile] u32
+// LDS: lines | noev[line][chunk] u64, lead[line][chunk + 1] u32 | flat rows [kPieceRows] 16 B | segoff[kSegments][kChains] u32 |
+//      scan scratch | same[kWaves][kChains + 1] | pieces [kPieceWords] | stage[tile] slots
 template <typename S, int ILV>
 __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restrict__ descs, const Work* __restrict__ works)
 {
@@ -744,15 +865,12 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
     S* s_rows = reinterpret_cast<S*>(smem + lds.rows);
     uint64_t* s_noev = reinterpret_cast<uint64_t*>(smem + lds.masks);                                // [line][chunk]
     uint32_t* s_lead = reinterpret_cast<uint32_t*>(s_noev + (size_t)w.lines_per_tile * chunks);       // [line][chunk + 1] (fits: 16 B per (line, chunk) reserved)
-    uint32_t* s_segoff = reinterpret_cast<uint32_t*>(smem + lds.table);                               // [kSegments][kChains]
-    uint32_t* s_tileoff = s_segoff + sort_segments(w.lines_per_tile) * kChains; // first local slot of the chain
-    uint32_t* s_count = s_tileoff + kChains + 1;          // events of the chain in this tile
-    uint32_t* s_global = s_count + kChains + 1;           // first global slot of the tile's piece
-    uint32_t* s_tmp = s_global + kChains + 1;             // kWaves words (+ padding to 16 words)
+    uint4* s_piecerows = reinterpret_cast<uint4*>(smem + lds.table);                                  // [kPieceRows] flat rows of the way out (P3)
+    uint32_t* s_segoff = reinterpret_cast<uint32_t*>(s_piecerows + kPieceRows);                       // [kSegments][kChains]
+    uint32_t* s_tmp = s_segoff + sort_segments(w.lines_per_tile) * kChains; // 2 * kWaves words
     uint32_t* s_same = s_tmp + 16;                        // [kWaves][kChains + 1] lanes of a chunk per chain, see P2; zero between uses
-    uint32_t* s_rowbase = s_same + kWaves * (kChains + 1); // [kChains + 1] first row of the chain's piece (P3)
-    uint16_t* s_rowchain = reinterpret_cast<uint16_t*>(s_rowbase + kChains + 1); // [slots of a tile / 64 + kChains + 1] (kRowChainWords words)
-    Slot<S>* s_stage = reinterpret_cast<Slot<S>*>(s_rowbase + kChains + 1 + kRowChainWords);
+    uint32_t* s_pieces = s_same + kWaves * (kChains + 1); // [kPieceWords] the tile's non-empty pieces (P3)
+    Slot<S>* s_stage = reinterpret_cast<Slot<S>*>(s_pieces + kPieceWords);
     const int mask = (1 << d.bits_per_sample) - 1;
     const Samples<S, ILV> sample{d, s_rows, g.first_line, mask};
     const auto key_tile = global_ptr(w.keyinv) + (size_t)g.first_line * width; // (read as keys, written as slots: P2)
@@ -764,6 +882,7 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
         s_segoff[i] = 0;
     for (uint32_t i = threadIdx.x; i < kWaves * ((uint32_t)kChains + 1); i += kThreads)
         s_same[i] = 0;
+    piece_tables_clear(s_piecerows, s_pieces);
     __syncthreads();
     JLS_PHASE(1);
     // ---- P1: events per (segment, chain), samples inside runs per chunk.  The keys of up to 16 chunks are requested before
@@ -861,16 +980,21 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
         if (chain)
             for (uint32_t sgm = 0; sgm < g.segments; ++sgm)
                 n += s_segoff[sgm * kChains + c];
-        // the pieces cut into rows of 64 records for the way out (P3): row q belongs to chain s_rowchain[q]; the interruption
-        // chain has no records
-        const uint32_t rows = chain && c != (uint32_t)kInterruptChain ? (n + 63) / 64 : 0u;
-        uint32_t off[2] = {n, 0}, row_base[2] = {rows, 0};
-        block_exclusive_scan_pair(off, row_base, kChains, s_tmp);
+        // the non-empty pieces numbered for the way out (P3, copy_pieces_out): the second series counts them.  The
+        // interruption chain has slots in the tile's local order and no records: the copy leaves its piece out.
+        const uint32_t global = chain ? global_ptr(w.seg)[(size_t)tile * kChains + c] : 0u;
+        uint32_t off[2] = {n, 0}, piece[2] = {n != 0 ? 1u : 0u, 0};
+        block_exclusive_scan_pair(off, piece, kChains, s_tmp);
         if (chain)
         {
-            s_tileoff[c] = off[0];
-            s_count[c] = n;
-            s_global[c] = global_ptr(w.seg)[(size_t)tile * kChains + c];
+            if (n != 0)
+            {
+                piece_tables_add(s_piecerows, s_pieces, piece[0], off[0], n, global);
+                if (c == (uint32_t)kInterruptChain)
+                    s_pieces[kChains + kPieceSkip] = piece[0];
+            }
+            if (c == (uint32_t)kChains - 1)
+                s_pieces[kChains + kPieceTotal] = off[0] + n;
             uint32_t running = off[0];
             for (uint32_t sgm = 0; sgm < g.segments; ++sgm)
             {
@@ -878,11 +1002,6 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
                 s_segoff[sgm * kChains + c] = running;
                 running += m;
             }
-            s_rowbase[c] = row_base[0];
-            for (uint32_t j = 0; j < rows; ++j)
-                s_rowchain[row_base[0] + j] = (uint16_t)c;
-            if (c == (uint32_t)kChains - 1)
-                s_rowbase[kChains] = row_base[0] + rows;
         }
     }
     JLS_PHASE(4);
@@ -1033,28 +1152,8 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
     __syncthreads();
     JLS_PHASE(7);
     // ---- P3: pieces out (the interruption chain has no records)
-    const uint32_t total_rows = s_rowbase[kChains];
-    constexpr int kRows = 4;
-    for (uint32_t q0 = (uint32_t)wave * kRows; q0 < total_rows; q0 += kWaves * kRows)
-    { // four rows at a time: their LDS reads overlap (eight: 1.5 % slower)
-        uint32_t to[kRows];
-        Slot<S> held[kRows];
-        bool live[kRows];
-#pragma unroll
-        for (int j = 0; j < kRows; ++j)
-        {
-            const uint32_t q = q0 + (uint32_t)j;
-            const uint32_t c = q < total_rows ? s_rowchain[q] : 0u;
-            const uint32_t i = (q - s_rowbase[c]) * 64 + (uint32_t)lane;
-            live[j] = q < total_rows && i < s_count[c];
-            to[j] = s_global[c] + i;
-            held[j] = live[j] ? s_stage[s_tileoff[c] + i] : (Slot<S>)0;
-        }
-#pragma unroll
-        for (int j = 0; j < kRows; ++j)
-            if (live[j])
-                global_ptr(rec_slots<S>(w))[to[j]] = held[j];
-    }
+    // (four flat rows at a time; eight were 1.5 % slower with the rows per piece of round 12)
+    copy_pieces_out<Slot<S>, 4>(s_piecerows, s_pieces, s_stage, global_ptr(rec_slots<S>(w)), kWaves);
     JLS_PHASE(8);
 }
 
@@ -1951,14 +2050,14 @@ __global__ void __launch_bounds__(64) settle_runs(const ScanDesc* __restrict__ d
 
 // ---------------------------------------------------------------------------------------------------------------
 // D: grid (tiles, scans) x 256; tiles in index order (a tile only waits for tiles that were started before it).
-// LDS: codes[tile] u32 | tileoff / count / global [kChains + 1] each | scan[256] | tmp
+// LDS: codes[tile] slots | scan[kPackThreads] | tmp | pieces [kPieceWords] | flat rows [kPieceRows] 16 B | bits
 #define JLS_HOST_DEV __host__ __device__ inline
 // LDS of pack_tiles: where the bit buffer starts (behind the code words, the piece tables and the row table)
 JLS_HOST_DEV uint32_t pack_bits_offset(uint32_t tile_capacity, uint32_t sample_bytes) // 16-byte aligned
 {
     const uint32_t codes = (uint32_t)stage_bytes(tile_capacity, sample_bytes);
-    const uint32_t head = ((codes + 3u) & ~3u) + 4 * ((uint32_t)kChains + 1) * 4 + kPackThreads * 4 + 16 * 4 + kRowChainWords * 4;
-    return (head + 15u) & ~15u;
+    const uint32_t head = ((codes + 3u) & ~3u) + kPackThreads * 4 + 16 * 4 + kPieceWords * 4;
+    return ((head + 15u) & ~15u) + kPieceRows * 16;
 }
 
 // Words of the bit buffer of pack_tiles: a sample's code has at most LIMIT = 2 (bpp + max(8, bpp)) bits (a run-length code
@@ -2013,14 +2112,12 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
     const uint32_t kPackWaves = threads / 64;
     Slot<S>* s_code = reinterpret_cast<Slot<S>*>(smem); // the tile's code words, in slots
     const uint32_t code_bytes = (uint32_t)stage_bytes(tile_capacity, (uint32_t)sizeof(S));
-    uint32_t* s_tileoff = reinterpret_cast<uint32_t*>(smem + ((code_bytes + 3u) & ~3u));
-    uint32_t* s_count = s_tileoff + kChains + 1;
-    uint32_t* s_global = s_count + kChains + 1;
-    uint32_t* s_scan = s_global + kChains + 1; // 256
+    uint32_t* s_scan = reinterpret_cast<uint32_t*>(smem + ((code_bytes + 3u) & ~3u)); // [kPackThreads]
     uint32_t* s_tmp = s_scan + kPackThreads;   // one word per wavefront (16 reserved)
-    uint32_t* s_rowbase = s_tmp + 16;          // [kChains + 1] first row of the chain's piece
-    uint16_t* s_rowchain = reinterpret_cast<uint16_t*>(s_rowbase + kChains + 1); // [slots of the tile / 64 + kChains + 1]: kRowChainWords words
-    uint32_t* s_bits = reinterpret_cast<uint32_t*>(smem + pack_bits_offset(tile_capacity, (uint32_t)sizeof(S))); // [pack_bits_words] the tile's bits
+    uint32_t* s_pieces = s_tmp + 16;           // [kPieceWords] the tile's non-empty pieces
+    const uint32_t bits_offset = pack_bits_offset(tile_capacity, (uint32_t)sizeof(S));
+    uint4* s_piecerows = reinterpret_cast<uint4*>(smem + bits_offset) - kPieceRows; // [kPieceRows] flat rows of the way into LDS
+    uint32_t* s_bits = reinterpret_cast<uint32_t*>(smem + bits_offset); // [pack_bits_words] the tile's bits
     const TileSpan span = tile_span(d, w, tile);
     const uint32_t tile_samples = span.count;
     const auto inv = global_ptr(w.keyinv) + span.first;
@@ -2050,10 +2147,11 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
             mine[q] = make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
         }
     }
-    { // the tile's pieces, chain by chain, in the order sort_tiles laid them out, and their rows: the pieces are cut into rows
-      // of 64 code words for the way into LDS; row q belongs to chain s_rowchain[q].  (One scan for both, see
-      // block_exclusive_scan_pair: a workgroup of fewer than kChains threads holds two chains per thread.)
-        uint32_t n[2] = {0, 0}, g[2] = {0, 0}, rows[2] = {0, 0};
+    piece_tables_clear(s_piecerows, s_pieces); // (the barriers of the scan below stand between this and piece_tables_add)
+    { // the tile's pieces, chain by chain, in the order sort_tiles laid them out, and the non-empty ones numbered for the way
+      // into LDS (copy_pieces_in).  (One scan for both, see block_exclusive_scan_pair: a workgroup of fewer than kChains
+      // threads holds two chains per thread.)
+        uint32_t n[2] = {0, 0}, g[2] = {0, 0};
         for (int half = 0; half < 2; ++half)
         {
             const uint32_t c = threadIdx.x + (uint32_t)half * threads;
@@ -2061,56 +2159,31 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
             {
                 g[half] = global_ptr(w.seg)[(size_t)tile * kChains + c];
                 n[half] = global_ptr(w.seg)[(size_t)(tile + 1) * kChains + c] - g[half];
-                rows[half] = (n[half] + 63) / 64;
             }
         }
-        uint32_t off[2] = {n[0], n[1]}, row_base[2] = {rows[0], rows[1]};
-        block_exclusive_scan_pair(off, row_base, kChains, s_tmp);
+        uint32_t off[2] = {n[0], n[1]}, piece[2] = {n[0] != 0 ? 1u : 0u, n[1] != 0 ? 1u : 0u};
+        block_exclusive_scan_pair(off, piece, kChains, s_tmp);
         for (int half = 0; half < 2; ++half)
         {
             const uint32_t c = threadIdx.x + (uint32_t)half * threads;
             if (c < (uint32_t)kChains)
             {
-                s_tileoff[c] = off[half];
-                s_count[c] = n[half];
-                s_global[c] = g[half];
-                s_rowbase[c] = row_base[half];
-                for (uint32_t j = 0; j < rows[half]; ++j)
-                    s_rowchain[row_base[half] + j] = (uint16_t)c;
+                if (n[half] != 0)
+                    piece_tables_add(s_piecerows, s_pieces, piece[half], off[half], n[half], g[half]);
+                if (c == 0)
+                    s_pieces[kChains + kPieceRun] = n[half];
                 if (c == (uint32_t)kChains - 1)
-                    s_rowbase[kChains] = row_base[half] + rows[half];
+                    s_pieces[kChains + kPieceTotal] = off[half] + n[half];
             }
         }
     }
     JLS_PHASE(9);
     __syncthreads();
     JLS_PHASE(11);
-    { // ---- the tile's code words into LDS.  A wavefront takes sixteen rows at a time and requests them together: fetched
-      // piece by piece (a piece is ~80 events on average, a few are hundreds), it spent its time waiting for one trip to
-      // memory per row.
-        const uint32_t total_rows = s_rowbase[kChains];
-        constexpr int kRows = 16; // rows a wavefront requests together
-        for (uint32_t q0 = (uint32_t)wave * kRows; q0 < total_rows; q0 += kPackWaves * kRows)
-        {
-            uint32_t to[kRows];
-            Slot<S> held[kRows];
-            bool live[kRows];
-#pragma unroll
-            for (int j = 0; j < kRows; ++j)
-            {
-                const uint32_t q = q0 + (uint32_t)j;
-                const uint32_t c = q < total_rows ? s_rowchain[q] : 0u;
-                const uint32_t i = (q - s_rowbase[c]) * 64 + (uint32_t)lane;
-                live[j] = q < total_rows && i < s_count[c];
-                to[j] = s_tileoff[c] + i;
-                held[j] = live[j] ? global_ptr(code_slots<S>(w))[s_global[c] + i] : (Slot<S>)0;
-            }
-#pragma unroll
-            for (int j = 0; j < kRows; ++j)
-                if (live[j])
-                    s_code[to[j]] = held[j];
-        }
-    }
+    // ---- the tile's code words into LDS.  A wavefront takes sixteen flat rows at a time and requests them together (a full
+    // tile of 8192 samples is one batch per wavefront): fetched row by row, it spent its time waiting for one trip to memory
+    // per row.
+    copy_pieces_in<Slot<S>, 16>(s_piecerows, s_pieces, global_ptr(code_slots<S>(w)), s_code, kPackWaves);
     JLS_PHASE(12);
     __syncthreads();
     JLS_PHASE(13);
@@ -2122,7 +2195,7 @@ __global__ void __launch_bounds__(kPackThreads) pack_tiles(const ScanDesc* __res
     };
     // The code word of the sample in `slot`, in the 32-bit form (length : 8 | bits : 24, or a run-length code): the entries of
     // the run chain come first in a tile's local order and take two of the 2-byte slots.
-    const uint32_t run_slots_end = kNarrow ? s_count[0] : 0u;
+    const uint32_t run_slots_end = kNarrow ? s_pieces[kChains + kPieceRun] : 0u;
     auto word_of = [&](uint32_t slot) -> uint32_t {
         if (slot == kNoLocalSlot)
             return 0u; // (no bits)
@@ -2342,8 +2415,8 @@ inline size_t analyze_lds_bytes(uint32_t width, uint32_t lines_per_tile, uint32_
 }
 inline size_t sort_lds_bytes(uint32_t width, uint32_t lines_per_tile, uint32_t sample_bytes, int interleave_mode)
 {
-    return tile_common_lds_bytes(width, lines_per_tile, sample_bytes, interleave_mode, false) + (size_t)sort_segments(lines_per_tile) * kChains * 4 +
-           4 * ((size_t)kChains + 1) * 4 + 16 * 4 + (size_t)kWaves * (kChains + 1) * 4 + kRowChainWords * 4 +
+    return tile_common_lds_bytes(width, lines_per_tile, sample_bytes, interleave_mode, false) + (size_t)kPieceRows * 16 +
+           (size_t)sort_segments(lines_per_tile) * kChains * 4 + 16 * 4 + (size_t)kWaves * (kChains + 1) * 4 + (size_t)kPieceWords * 4 +
            stage_bytes((uint32_t)lines_per_tile * width, sample_bytes);
 }
 // Threads of a pack_tiles workgroup: 512 with 8 or 16 consecutive samples each; a tile that would leave more than a fifth of

@@ -552,15 +552,12 @@ __global__ void __launch_bounds__(kThreads) sort_pixel_tiles(const ScanDesc* __r
     S* s_rows = reinterpret_cast<S*>(smem + lds.rows);
     uint64_t* s_noev = reinterpret_cast<uint64_t*>(smem + lds.masks);                               // [row][chunk]
     uint32_t* s_lead = reinterpret_cast<uint32_t*>(s_noev + (size_t)w.lines_per_tile * max_chunks); // [row][chunk + 1]
-    uint32_t* s_segoff = reinterpret_cast<uint32_t*>(smem + lds.table);                             // [kSegments][kChains]
-    uint32_t* s_tileoff = s_segoff + sort_segments(w.lines_per_tile) * kChains;
-    uint32_t* s_count = s_tileoff + kChains + 1;
-    uint32_t* s_global = s_count + kChains + 1;
-    uint32_t* s_tmp = s_global + kChains + 1;
+    uint4* s_piecerows = reinterpret_cast<uint4*>(smem + lds.table);                                // [kPieceRows]
+    uint32_t* s_segoff = reinterpret_cast<uint32_t*>(s_piecerows + kPieceRows);                     // [kSegments][kChains]
+    uint32_t* s_tmp = s_segoff + sort_segments(w.lines_per_tile) * kChains;
     uint32_t* s_same = s_tmp + 16;
-    uint32_t* s_rowbase = s_same + kWaves * (kChains + 1);
-    uint16_t* s_rowchain = reinterpret_cast<uint16_t*>(s_rowbase + kChains + 1);
-    Slot<S>* s_stage = reinterpret_cast<Slot<S>*>(s_rowbase + kChains + 1 + kRowChainWords);
+    uint32_t* s_pieces = s_same + kWaves * (kChains + 1);                                           // [kPieceWords]
+    Slot<S>* s_stage = reinterpret_cast<Slot<S>*>(s_pieces + kPieceWords);
     const int mask = (1 << d.bits_per_sample) - 1;
     auto key_row = [&](uint32_t r) -> uint16_t* { return w.keyinv + (size_t)(g.first_line + r) * g.line_samples + (size_t)g.px0 * nc; };
 
@@ -569,6 +566,7 @@ __global__ void __launch_bounds__(kThreads) sort_pixel_tiles(const ScanDesc* __r
         s_segoff[i] = 0;
     for (uint32_t i = threadIdx.x; i < kWaves * ((uint32_t)kChains + 1); i += kThreads)
         s_same[i] = 0;
+    piece_tables_clear(s_piecerows, s_pieces);
     __syncthreads();
     // ---- P1: events per (segment, chain), samples inside runs per chunk
     for (uint32_t sgm = wave; sgm < segments; sgm += kWaves)
@@ -613,16 +611,18 @@ __global__ void __launch_bounds__(kThreads) sort_pixel_tiles(const ScanDesc* __r
                 for (uint32_t sgm = 0; sgm < segments; ++sgm)
                     n[half] += s_segoff[sgm * kChains + c];
         }
-        uint32_t off[2] = {n[0], n[1]};
-        block_exclusive_scan(off[0], off[1], s_tmp);
+        // (the second series numbers the non-empty pieces for the way out: copy_pieces_out)
+        uint32_t off[2] = {n[0], n[1]}, piece[2] = {n[0] != 0 ? 1u : 0u, n[1] != 0 ? 1u : 0u};
+        block_exclusive_scan_pair(off, piece, kChains, s_tmp);
         for (int half = 0; half < 2; ++half)
         {
             const uint32_t c = threadIdx.x + (uint32_t)half * kThreads;
             if (c < (uint32_t)kChains)
             {
-                s_tileoff[c] = off[half];
-                s_count[c] = n[half];
-                s_global[c] = w.seg[(size_t)tile * kChains + c];
+                if (n[half] != 0)
+                    piece_tables_add(s_piecerows, s_pieces, piece[half], off[half], n[half], w.seg[(size_t)tile * kChains + c]);
+                if (c == (uint32_t)kChains - 1)
+                    s_pieces[kChains + kPieceTotal] = off[half] + n[half];
                 uint32_t running = off[half];
                 for (uint32_t sgm = 0; sgm < segments; ++sgm)
                 {
@@ -630,25 +630,6 @@ __global__ void __launch_bounds__(kThreads) sort_pixel_tiles(const ScanDesc* __r
                     s_segoff[sgm * kChains + c] = running;
                     running += m;
                 }
-            }
-        }
-        uint32_t rows[2], row_base[2];
-        for (int half = 0; half < 2; ++half)
-        {
-            const uint32_t c = threadIdx.x + (uint32_t)half * kThreads;
-            rows[half] = row_base[half] = c < (uint32_t)kChains ? (n[half] + 63) / 64 : 0u;
-        }
-        block_exclusive_scan(row_base[0], row_base[1], s_tmp);
-        for (int half = 0; half < 2; ++half)
-        {
-            const uint32_t c = threadIdx.x + (uint32_t)half * kThreads;
-            if (c < (uint32_t)kChains)
-            {
-                s_rowbase[c] = row_base[half];
-                for (uint32_t j = 0; j < rows[half]; ++j)
-                    s_rowchain[row_base[half] + j] = (uint16_t)c;
-                if (c == (uint32_t)kChains - 1)
-                    s_rowbase[kChains] = row_base[half] + rows[half];
             }
         }
         if (threadIdx.x >= kThreads - g.tile_lines)
@@ -786,27 +767,7 @@ __global__ void __launch_bounds__(kThreads) sort_pixel_tiles(const ScanDesc* __r
     }
     __syncthreads();
     // ---- P3: pieces out
-    const uint32_t total_rows = s_rowbase[kChains];
-    for (uint32_t q0 = (uint32_t)wave * 4; q0 < total_rows; q0 += kWaves * 4)
-    {
-        uint32_t to[4];
-        Slot<S> held[4];
-        bool live[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-        {
-            const uint32_t q = q0 + (uint32_t)j;
-            const uint32_t c = q < total_rows ? s_rowchain[q] : 0u;
-            const uint32_t i = (q - s_rowbase[c]) * 64 + (uint32_t)lane;
-            live[j] = q < total_rows && i < s_count[c];
-            to[j] = s_global[c] + i;
-            held[j] = live[j] ? s_stage[s_tileoff[c] + i] : (Slot<S>)0;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (live[j])
-                rec_slots<S>(w)[to[j]] = held[j];
-    }
+    copy_pieces_out<Slot<S>, 4>(s_piecerows, s_pieces, s_stage, global_ptr(rec_slots<S>(w)), kWaves);
 }
 
 inline size_t analyze_pixel_lds_bytes(uint32_t lines_per_tile, uint32_t step, uint32_t max_pixels, uint32_t nc, uint32_t sample_bytes, uint32_t tile_capacity)
@@ -817,8 +778,8 @@ inline size_t analyze_pixel_lds_bytes(uint32_t lines_per_tile, uint32_t step, ui
 inline size_t sort_pixel_lds_bytes(uint32_t lines_per_tile, uint32_t step, uint32_t max_pixels, uint32_t nc, uint32_t sample_bytes, uint32_t tile_capacity)
 {
     const PixelLds l = pixel_lds(lines_per_tile, step, max_pixels, nc, sample_bytes, tile_capacity, false, (max_pixels * nc + 63) / 64);
-    return (size_t)l.table + (size_t)sort_segments(lines_per_tile) * kChains * 4 + 4 * ((size_t)kChains + 1) * 4 + 16 * 4 +
-           (size_t)kWaves * (kChains + 1) * 4 + kRowChainWords * 4 + stage_bytes(tile_capacity, sample_bytes);
+    return (size_t)l.table + (size_t)kPieceRows * 16 + (size_t)sort_segments(lines_per_tile) * kChains * 4 + 16 * 4 +
+           (size_t)kWaves * (kChains + 1) * 4 + (size_t)kPieceWords * 4 + stage_bytes(tile_capacity, sample_bytes);
 }
 
 } // namespace tile

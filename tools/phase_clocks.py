@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where the wavefronts of sort_tiles / pack_tiles spend their clocks (a debug build: the marks of JLS_PHASE in
+"""Where the wavefronts of analyze_tiles / sort_tiles / pack_tiles spend their clocks (a debug build: the marks of JLS_PHASE in
 tile_pipeline.hip count only when the library is built with CHARLS_AMD_CXXFLAGS=-DJLS_PHASE_CLOCKS).
 
     CHARLS_AMD_CXXFLAGS=-DJLS_PHASE_CLOCKS python charls_amd/build.py --force      (here)
@@ -16,10 +16,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {
+    "analyze_tiles": {22: "lines requested", 23: "tables zeroed + barrier (lines arrive)", 24: "pass 1 contexts, masks", 25: "barrier",
+                      26: "pass 2 run states, keys out, histogram", 27: "barrier, histogram out"},
     "sort_tiles": {0: "lines requested", 1: "tables zeroed + barrier (lines arrive)", 2: "P1 keys, histogram", 3: "barrier",
                    4: "run leads, offsets", 5: "barrier", 6: "P2 ranks, records", 7: "barrier", 8: "P3 pieces out"},
     # (in the order of the kernel: the bits go into LDS before the look-back)
-    "pack_tiles": {9: "slot map requested, piece and row tables", 11: "barrier", 12: "code words into LDS", 13: "barrier",
+    "pack_tiles": {9: "slot map requested, piece and flat-row tables", 11: "barrier", 12: "code words into LDS", 13: "barrier",
                    14: "bits of the thread's samples", 15: "scan of the bit counts", 18: "bits into LDS", 19: "barrier",
                    16: "look-back, shared words (wavefront 0)", 20: "barrier (the others wait for wavefront 0)", 21: "words out"},
 }
