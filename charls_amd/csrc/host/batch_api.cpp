@@ -15,40 +15,17 @@
 #include "../device/runtime.h"
 #include "batch_streams.h"
 #include "common.h"
+#include "event_timer.h"
 #include "preset.h"
+#include "seek_index.h"
 #include "stream_reader.h"
+#include "stream_windows.h"
 #include "stream_writer.h"
-#include "window_fetch.h"
 
 using namespace jls;
 using dev::hip_check;
 
 namespace {
-struct EventTimer
-{
-    hipEvent_t a{}, b{};
-    hipStream_t s;
-    explicit EventTimer(hipStream_t stream) : s(stream)
-    {
-        hip_check(hipEventCreate(&a));
-        hip_check(hipEventCreate(&b));
-    }
-    ~EventTimer()
-    {
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-    }
-    void start() { hip_check(hipEventRecord(a, s)); }
-    void stop() { hip_check(hipEventRecord(b, s)); }
-    double ms()
-    {
-        float v = 0;
-        hip_check(hipEventSynchronize(b));
-        hip_check(hipEventElapsedTime(&v, a, b));
-        return v;
-    }
-};
-
 // Validation of the coding parameters: the checks charls_jpegls_encoder::encode_components performs before any scan
 // is coded (reference src/charls_jpegls_encoder.cpp:182-207, 298-358).
 void validate_encode(const charls_amd_codec_params& p, size_t frame_pitch, uint32_t stride_arg, size_t* stride_out,
@@ -101,23 +78,12 @@ void validate_encode(const charls_amd_codec_params& p, size_t frame_pitch, uint3
     *stride_out = stride;
 }
 
-ScanDesc base_desc(const charls_frame_info& f, int32_t components, int32_t ilv, int32_t near, int32_t xform,
-                   const charls_jpegls_pc_parameters& pc, uint32_t restart)
+// A scan of the frames of `p`: one component of a planar frame, all of them otherwise (pc: validated).
+ScanSpec scan_spec_for(const charls_amd_codec_params& p, const charls_jpegls_pc_parameters& pc) noexcept
 {
-    ScanDesc d{};
-    d.width = f.width;
-    d.height = f.height;
-    d.components = components;
-    d.interleave_mode = ilv;
-    d.bits_per_sample = f.bits_per_sample;
-    d.near_lossless = near;
-    d.color_transformation = xform;
-    d.t1 = pc.threshold1;
-    d.t2 = pc.threshold2;
-    d.t3 = pc.threshold3;
-    d.reset = static_cast<uint8_t>(pc.reset_value);
-    d.restart_interval = restart;
-    return d;
+    const charls_frame_info& f = p.frame_info;
+    return ScanSpec{f.width, f.height, p.interleave_mode == 0 ? 1 : f.component_count, p.interleave_mode, f.bits_per_sample,
+                    p.near_lossless, p.color_transformation, pc, p.restart_interval};
 }
 
 // The container bytes in front of a frame's first scan, by the writer of part 1; returns their number.
@@ -165,7 +131,7 @@ EncodePlan jls::plan_encode(const charls_amd_codec_params& p, size_t frame_bytes
     const charls_frame_info& f = p.frame_info;
     plan.scans = p.interleave_mode == 0 ? static_cast<uint32_t>(f.component_count) : 1u;
     const int32_t comps_per_scan = p.interleave_mode == 0 ? 1 : f.component_count;
-    plan.scan = base_desc(f, comps_per_scan, p.interleave_mode, p.near_lossless, p.color_transformation, pc, p.restart_interval);
+    plan.scan = desc_of(scan_spec_for(p, pc));
     plan.scan.pixel_stride = plan.stride;
     uint8_t prologue[512];
     plan.container_bytes = write_prologue(p, pc, prologue, sizeof prologue);
@@ -237,6 +203,7 @@ void jls::encode_batch_frames(const charls_amd_codec_params& p, uint32_t frame_c
     hip_check(hipMemcpyAsync(d_blob.as<uint8_t>(), blob.data(), blob_bytes, hipMemcpyHostToDevice, stream));
 
     std::vector<ScanDesc> descs(frame_count);
+    const ScanDesc scan = desc_of(scan_spec_for(p, pc)); // every scan of every frame, without its pointers
     auto* slots = static_cast<uint8_t*>(d_streams);
 
     EventTimer total(stream), scans(stream);
@@ -291,7 +258,8 @@ void jls::encode_batch_frames(const charls_amd_codec_params& p, uint32_t frame_c
             for (uint32_t i = 0; i < n; ++i)
                 for (uint32_t r = 0; r < rounds; ++r)
                 {
-                    ScanDesc d = base_desc(f, 1, 0, p.near_lossless, p.color_transformation, pc, 0);
+                    ScanDesc d = scan; // (one component, ILV_NONE, no restart intervals: this branch's condition above has
+                                       // rounds > 1, which only planar frames have, and p.restart_interval == 0)
                     d.pixels = const_cast<uint8_t*>(frames[first + i]) + r * stride * f.height;
                     d.pixel_stride = stride;
                     d.stream = priv + (static_cast<size_t>(i) * rounds + r) * capacity;
@@ -325,8 +293,7 @@ void jls::encode_batch_frames(const charls_amd_codec_params& p, uint32_t frame_c
     {
         for (uint32_t i = 0; i < frame_count; ++i)
         {
-            ScanDesc d = base_desc(f, comps_per_scan, p.interleave_mode, p.near_lossless, p.color_transformation, pc,
-                                   p.restart_interval);
+            ScanDesc d = scan;
             d.pixels = const_cast<uint8_t*>(frames[i]) + (p.interleave_mode == 0 ? r * stride * f.height : 0);
             d.pixel_stride = stride;
             d.line_scratch = d_scratch.as<uint16_t>() + i * scratch_samples;
@@ -428,450 +395,276 @@ void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, cons
     decode_batch_streams(frame_count, d_streams, stream_at, sizes, BatchDests{dests.data(), false, nullptr}, params_out, errcs, hip_stream);
 }
 
-// The batch decoder behind charls_amd_decode_batch_device (slots: stream_at[i] = i * pitch),
-// charls_amd_decode_batch_device_packed (batch_packed.cpp: stream_at = the caller's offset table) and the calls of part 2e
-// (batch_ragged.cpp: a destination per frame, or none -- the probe): frame i's stream is the sizes[i] bytes at
-// d_streams + stream_at[i] and goes to to.dests[i].  frame_count >= 1, the pointers are checked by the entry points.
-void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, const uint64_t* stream_at, const uint64_t* sizes,
-                               const BatchDests& to, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs,
-                               void* hip_stream)
+namespace {
+
+// The probe: part 1's get_destination_size(stride 0) (decoder_api.cpp: destination_size) beside the parameters; an
+// abbreviated table stream has no frame: read_header succeeds on it, and it reports zeros.
+void probe_frames(StreamWindows& win, const BatchDests& to, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs)
 {
-    dev::require_device();
-    auto stream = static_cast<hipStream_t>(hip_stream);
-    const auto* slots = static_cast<const uint8_t*>(d_streams);
-    const bool probing = to.dests == nullptr;
-
-    // Every frame's marker segments are parsed on the host by the part-1 reader.  Only a window of each stream is
-    // fetched: the first `kWindow` bytes up front, later windows at the position each scan ended.
-    constexpr size_t kWindow = 2048;
-    struct Frame
+    for (uint32_t i = 0; i < win.fr.size(); ++i)
     {
-        StreamReader reader;
-        std::vector<uint8_t> window; // host copy of [window_base, window_base + window.size())
-        size_t window_base{};
-        size_t cursor{};             // absolute offset of the next unparsed byte
-        size_t plane_offset{};       // destination offset of the next scan
-        uint32_t decoded_components{};
-        charls_jpegls_errc errc{};
-        bool done{};
-    };
-    std::vector<Frame> fr(frame_count);
-
-    auto fetch = [&](Frame& x, uint32_t i, size_t base, size_t bytes) {
-        const size_t avail = base < sizes[i] ? static_cast<size_t>(sizes[i]) - base : 0;
-        const size_t n = std::min(bytes, avail);
-        x.window.resize(n);
-        x.window_base = base;
-        if (n)
-            hip_check(hipMemcpyAsync(x.window.data(), slots + stream_at[i] + base, n, hipMemcpyDeviceToHost, stream));
-    };
-    // the same for many frames at once (bases[k] is the offset of frame which[k]'s window): one gather on the device, one copy
-    dev::DeviceBuffer d_specs, d_windows;
-    dev::PinnedBuffer h_specs, h_windows;
-    auto fetch_many = [&](std::vector<Frame>& set, const std::vector<uint32_t>& which, const std::vector<size_t>& bases) {
-        const size_t n = which.size();
-        if (n == 0)
-            return;
-        auto* specs = static_cast<WindowSpec*>(h_specs.ensure(sizeof(WindowSpec) * n));
-        for (size_t k = 0; k < n; ++k)
-        {
-            const uint32_t i = which[k];
-            const size_t avail = bases[k] < sizes[i] ? static_cast<size_t>(sizes[i]) - bases[k] : 0;
-            specs[k] = WindowSpec{stream_at[i] + bases[k],
-                                  static_cast<uint32_t>(std::min(kWindow, avail)), 0};
-        }
-        d_specs.ensure(sizeof(WindowSpec) * n);
-        d_windows.ensure(kWindow * n);
-        auto* staged = static_cast<uint8_t*>(h_windows.ensure(kWindow * n));
-        hip_check(hipMemcpyAsync(d_specs.as<WindowSpec>(), specs, sizeof(WindowSpec) * n, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(gather_windows, dim3(static_cast<uint32_t>(n)), dim3(256), 0, stream, slots, d_specs.as<const WindowSpec>(),
-                           d_windows.as<uint8_t>(), static_cast<uint32_t>(kWindow));
-        hip_check(hipGetLastError());
-        hip_check(hipMemcpyAsync(staged, d_windows.as<uint8_t>(), kWindow * n, hipMemcpyDeviceToHost, stream));
-        hip_check(hipStreamSynchronize(stream));
-        for (size_t k = 0; k < n; ++k)
-        {
-            Frame& x = set[which[k]];
-            x.window.assign(staged + k * kWindow, staged + k * kWindow + specs[k].bytes);
-            x.window_base = bases[k];
-        }
-    };
-    // A parse that runs off the end of the window while the stream has more bytes is retried with a larger window.
-    auto parse = [&](std::vector<Frame>& set, uint32_t i, auto&& body) {
-        Frame& x = set[i];
-        size_t want = kWindow;
-        const StreamReader snapshot = x.reader; // a failed attempt may have advanced the reader's state machine
-        for (;;)
-        {
+        BatchFrame& x = win.fr[i];
+        params_out[i] = charls_amd_codec_params{};
+        to.frame_bytes_out[i] = 0;
+        if (x.errc == CHARLS_JPEGLS_ERRC_SUCCESS && !x.reader.end_of_image())
             try
             {
-                body(x);
-                x.errc = CHARLS_JPEGLS_ERRC_SUCCESS;
-                return;
+                const charls_frame_info& f = x.reader.frame_info();
+                to.frame_bytes_out[i] = checked_mul(checked_mul(checked_mul(static_cast<size_t>(f.component_count), f.height), f.width),
+                                                    bytes_per_sample(f.bits_per_sample));
+                params_out[i] = params_of(x.reader);
             }
             catch (const error& e)
             {
-                const bool truncated = x.window_base + x.window.size() < sizes[i];
-                if (!truncated || (e.code != CHARLS_JPEGLS_ERRC_NEED_MORE_DATA &&
-                                   e.code != CHARLS_JPEGLS_ERRC_INVALID_MARKER_SEGMENT_SIZE &&
-                                   e.code != CHARLS_JPEGLS_ERRC_DEFINE_NUMBER_OF_LINES_MARKER_NOT_FOUND))
-                {
-                    x.errc = e.code;
-                    x.done = true;
-                    return;
-                }
+                x.errc = e.code;
             }
-            want *= 8;
-            fetch(x, i, x.window_base, want);
-            hip_check(hipStreamSynchronize(stream));
-            x.reader = snapshot;
-        }
-    };
-
-    {
-        std::vector<uint32_t> all(frame_count);
-        for (uint32_t i = 0; i < frame_count; ++i)
-            all[i] = i;
-        fetch_many(fr, all, std::vector<size_t>(frame_count, 0));
+        errcs[i] = x.errc;
     }
-    for (uint32_t i = 0; i < frame_count; ++i)
-        parse(fr, i, [&](Frame& x) {
-            x.reader.set_source(x.window.data(), x.window.size());
-            x.reader.read_header();
-            if (x.reader.end_of_image() && !probing)
-                raise(CHARLS_JPEGLS_ERRC_INVALID_OPERATION); // abbreviated table stream: nothing to decode
-            x.cursor = x.window_base + static_cast<size_t>(x.reader.position() - x.window.data());
-        });
+    dev::Timings& t = dev::last_timings(); // (no kernel of the decoder ran)
+    t.values[0] = t.values[1] = 0;
+    t.count = 2;
+}
 
-    // What params_out says about a frame whose reader stands behind the header of its first scan.
-    auto params_of = [](const StreamReader& r) {
-        return charls_amd_codec_params{r.frame_info(), r.parameters().near_lossless, r.scan_interleave_mode(), r.parameters().transformation,
-                                       r.preset_coding_parameters(), 0, r.parameters().restart_interval};
-    };
-    if (probing)
+// A destination per frame of the caller's own: stride and capacity against the whole frame -- the rows of all planes of a
+// planar frame --, before any of its scans is decoded.
+void check_ragged_dests(StreamWindows& win, const BatchDests& to)
+{
+    for (uint32_t i = 0; i < win.fr.size(); ++i)
     {
-        // part 1's get_destination_size(stride 0) (decoder_api.cpp: destination_size) beside the parameters; an abbreviated
-        // table stream has no frame: read_header succeeds on it, and it reports zeros
-        for (uint32_t i = 0; i < frame_count; ++i)
-        {
-            Frame& x = fr[i];
-            params_out[i] = charls_amd_codec_params{};
-            to.frame_bytes_out[i] = 0;
-            if (x.errc == CHARLS_JPEGLS_ERRC_SUCCESS && !x.reader.end_of_image())
-                try
-                {
-                    const charls_frame_info& f = x.reader.frame_info();
-                    to.frame_bytes_out[i] = checked_mul(checked_mul(checked_mul(static_cast<size_t>(f.component_count), f.height), f.width),
-                                                        bytes_per_sample(f.bits_per_sample));
-                    params_out[i] = params_of(x.reader);
-                }
-                catch (const error& e)
-                {
-                    x.errc = e.code;
-                }
-            errcs[i] = x.errc;
-        }
-        dev::Timings& t = dev::last_timings(); // (no kernel of the decoder ran)
-        t.values[0] = t.values[1] = 0;
-        t.count = 2;
-        return;
-    }
-    // A destination per frame of the caller's own: stride and capacity against the whole frame -- the rows of all planes of a
-    // planar frame --, before any of its scans is decoded.
-    for (uint32_t i = 0; i < frame_count && to.ragged; ++i)
-    {
-        Frame& x = fr[i];
+        BatchFrame& x = win.fr[i];
         if (x.done)
             continue;
-        const charls_frame_info& f = x.reader.frame_info();
-        const int32_t ilv = x.reader.scan_interleave_mode();
-        const size_t row = (ilv == 0 ? 1u : x.reader.scan_component_count()) * static_cast<size_t>(f.width) * bytes_per_sample(f.bits_per_sample);
-        const size_t rows = static_cast<size_t>(f.height) * (ilv == 0 ? x.reader.component_count() : 1u);
-        const size_t stride = to.dests[i].stride == 0 ? row : to.dests[i].stride;
+        const auto [row, stride] = row_and_stride(x.reader, to.dests[i].stride);
+        const size_t rows = static_cast<size_t>(x.reader.frame_info().height) * scans_of_frame(x.reader);
         if (stride < row)
             x.errc = CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_STRIDE;
         else if (to.dests[i].capacity_bytes < stride * rows - (stride - row))
             x.errc = CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE;
         x.done = x.errc != CHARLS_JPEGLS_ERRC_SUCCESS;
     }
+}
 
-    dev::DeviceBuffer d_descs, d_results, d_scratch;
-    std::vector<ScanDesc> descs;
-    std::vector<ScanResult> results;
-    std::vector<uint32_t> active;
-    EventTimer total(stream);
-    double scan_ms = 0;
-    uint32_t params_from = UINT32_MAX; // the frame params_out describes so far: the lowest-index frame that got as far as a scan
+// A decode past the headers: the streams, the launches, where the frames go and what the caller learns of their parameters.
+struct BatchDecode
+{
+    StreamWindows& win;
+    DecodeLauncher& launcher;
+    const BatchDests& to;
+    charls_amd_codec_params* params_out;
+    uint32_t params_from; // the frame params_out describes so far: the lowest-index frame that got as far as a scan
+};
 
-    // What a frame's scan needs besides its stream position: geometry and coding parameters from the reader (which stands
-    // behind the scan's header), the destination of its first plane, the line scratch (an offset until run_scans places it).
-    auto scan_desc = [&](uint32_t i, Frame& x, size_t& scratch_total) -> ScanDesc {
-        const charls_frame_info& f = x.reader.frame_info();
-        const int32_t ilv = x.reader.scan_interleave_mode();
-        const uint32_t nc = x.reader.scan_component_count();
-        const size_t row = (ilv == 0 ? 1u : nc) * static_cast<size_t>(f.width) * bytes_per_sample(f.bits_per_sample);
-        size_t stride = to.dests[i].stride;
-        if (stride == 0)
-            stride = row;
-        else if (stride < row)
-            raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_STRIDE);
-        const size_t need = (ilv == 0 ? stride * nc * f.height : stride * f.height) - (stride - row);
-        if (to.dests[i].capacity_bytes < x.plane_offset + need)
-            raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
-        ScanDesc d = base_desc(f, static_cast<int32_t>(nc), ilv, x.reader.parameters().near_lossless,
-                               x.reader.parameters().transformation, x.reader.validated_pc(),
-                               x.reader.parameters().restart_interval);
-        d.pixels = static_cast<uint8_t*>(to.dests[i].d_pixels) + x.plane_offset;
-        d.pixel_stride = stride;
-        d.stream = const_cast<uint8_t*>(slots) + stream_at[i] + x.cursor;
-        d.stream_capacity = sizes[i] - x.cursor;
-        d.line_scratch = reinterpret_cast<uint16_t*>(scratch_total); // placed by run_scans
-        scratch_total += dev::line_scratch_samples(f.width, ilv, static_cast<int32_t>(nc)) * sizeof(uint16_t);
-        scratch_total = (scratch_total + 255) & ~size_t{255};
-        return d;
-    };
-    auto report_params = [&](Frame& x, uint32_t index) {
-        if (params_out && to.ragged)
-            params_out[index] = params_of(x.reader);
-        else if (params_out && index < params_from)
-        {
-            *params_out = params_of(x.reader);
-            params_from = index;
-        }
-    };
-    // Decodes descs[0, n) (tags[k] says whose scan descs[k] is; both are permuted: scans that can share a kernel
-    // specialisation are made contiguous, one launch per group) and leaves results[k] beside descs[k].
-    auto run_scans = [&](std::vector<uint32_t>& tags, size_t scratch_total) {
-        const uint32_t n = static_cast<uint32_t>(descs.size());
-        auto* scratch = static_cast<uint8_t*>(d_scratch.ensure(scratch_total));
-        for (ScanDesc& d : descs)
-            d.line_scratch = reinterpret_cast<uint16_t*>(scratch + reinterpret_cast<size_t>(d.line_scratch));
-        {
-            std::vector<uint32_t> order(n);
-            for (uint32_t k = 0; k < n; ++k)
-                order[k] = k;
-            std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-                return dev::decode_launch_key(descs[a]) < dev::decode_launch_key(descs[b]);
-            });
-            std::vector<ScanDesc> d2(n);
-            std::vector<uint32_t> t2(n);
-            for (uint32_t k = 0; k < n; ++k)
-            {
-                d2[k] = descs[order[k]];
-                t2[k] = tags[order[k]];
-            }
-            descs = std::move(d2);
-            tags = std::move(t2);
-        }
-        d_descs.ensure(sizeof(ScanDesc) * n);
-        d_results.ensure(sizeof(ScanResult) * n);
-        results.resize(n);
-        hip_check(hipMemcpyAsync(d_descs.as<ScanDesc>(), descs.data(), sizeof(ScanDesc) * n, hipMemcpyHostToDevice, stream));
-        total.start();
-        for (uint32_t first = 0; first < n;)
-        {
-            uint32_t last = first + 1;
-            while (last < n && dev::decode_launch_key(descs[last]) == dev::decode_launch_key(descs[first]))
-                ++last;
-            dev::launch_decode(descs[first], d_descs.as<ScanDesc>() + first, d_results.as<ScanResult>() + first, last - first,
-                               stream);
-            first = last;
-        }
-        total.stop();
-        hip_check(hipMemcpyAsync(results.data(), d_results.as<ScanResult>(), sizeof(ScanResult) * n, hipMemcpyDeviceToHost, stream));
-        hip_check(hipStreamSynchronize(stream)); // (descs and results are reused by the next call)
-        scan_ms += total.ms();
-    };
+// What a frame's scan needs besides its stream position: geometry and coding parameters from the reader (which stands
+// behind the scan's header), the destination of its first plane.  The launcher places the line scratch.
+ScanDesc scan_desc_for(const BatchDecode& b, uint32_t i, const BatchFrame& x)
+{
+    const charls_frame_info& f = x.reader.frame_info();
+    const auto [row, stride] = row_and_stride(x.reader, b.to.dests[i].stride);
+    if (stride < row)
+        raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_STRIDE);
+    const uint32_t nc = x.reader.scan_component_count();
+    const size_t need = (x.reader.scan_interleave_mode() == 0 ? stride * nc * f.height : stride * f.height) - (stride - row);
+    if (b.to.dests[i].capacity_bytes < x.plane_offset + need)
+        raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+    ScanDesc d = desc_of(scan_spec_of(x.reader));
+    d.pixels = static_cast<uint8_t*>(b.to.dests[i].d_pixels) + x.plane_offset;
+    d.pixel_stride = stride;
+    d.stream = b.win.stream_ptr(i, x.cursor);
+    d.stream_capacity = b.win.sizes[i] - x.cursor;
+    return d;
+}
 
-    // ---- Planar frames: the component scans of all of them in ONE launch (the decoder's rate is the number of scans in
-    // flight: scan by scan, a batch of RGB planes ran three rounds of a third of its scans).  Where scan c + 1 starts is only
-    // known once scan c has been decoded -- or once the marker that ends scan c has been found: inside an entropy-coded
-    // segment no 0xFF is followed by a byte with its high bit set, so a search finds it (find_scan_end), and the part-1 reader
-    // parses on from there, on a COPY of the frame's state.  The copy replaces the frame only if every scan then ends exactly
-    // at the marker found behind it and the end of the image parses; any frame that does not is decoded again by the rounds
-    // below, which report whatever part 1 reports for it.  src/charls_jpegls_decoder.cpp:211-236 is the scan-by-scan loop.
-    if (knobs::get_or(knobs::kBatchRounds, 0) == 0)
+void report_params(BatchDecode& b, const BatchFrame& x, uint32_t index)
+{
+    if (b.params_out && b.to.ragged)
+        b.params_out[index] = params_of(x.reader);
+    else if (b.params_out && index < b.params_from)
     {
-        struct Plan
-        {
-            uint32_t frame;
-            std::vector<ScanDesc> scans;   // (line scratch: an offset until run_scans places it)
-            std::vector<size_t> starts;    // first byte of scan c
-            std::vector<size_t> marker_at; // the marker found behind scan c
-            bool ok{true};
-        };
-        std::vector<Frame> probe;
-        std::vector<Plan> plans;
-        size_t scratch_total = 0;
-        for (uint32_t i = 0; i < frame_count; ++i)
-        {
-            const Frame& x = fr[i];
-            if (x.done || x.reader.component_count() < 2 || x.reader.scan_interleave_mode() != 0 || x.reader.scan_component_count() != 1)
+        *b.params_out = params_of(x.reader);
+        b.params_from = index;
+    }
+}
+
+// A planar frame whose component scans go in the one launch of decode_planar_in_one_launch.
+struct Plan
+{
+    uint32_t frame;
+    std::vector<ScanDesc> scans;
+    std::vector<size_t> starts;    // first byte of scan c
+    std::vector<size_t> marker_at; // the marker found behind scan c
+    std::vector<size_t> used;      // bytes scan c consumed
+    size_t first_desc{};           // its scans in the launch
+    bool ok{true};
+};
+
+// ---- Planar frames: the component scans of all of them in ONE launch (the decoder's rate is the number of scans in
+// flight: scan by scan, a batch of RGB planes ran three rounds of a third of its scans).  Where scan c + 1 starts is only
+// known once scan c has been decoded -- or once the marker that ends scan c has been found: inside an entropy-coded
+// segment no 0xFF is followed by a byte with its high bit set, so a search finds it (find_scan_end), and the part-1 reader
+// parses on from there, on a COPY of the frame's state.  The copy replaces the frame only if every scan then ends exactly
+// at the marker found behind it and the end of the image parses; any frame that does not is decoded again by the rounds
+// below, which report whatever part 1 reports for it.  src/charls_jpegls_decoder.cpp:211-236 is the scan-by-scan loop.
+void decode_planar_in_one_launch(BatchDecode& b)
+{
+    StreamWindows& win = b.win;
+    std::vector<BatchFrame>& fr = win.fr;
+    const hipStream_t stream = win.stream;
+    std::vector<BatchFrame> probe;
+    std::vector<Plan> plans;
+    for (uint32_t i = 0; i < fr.size(); ++i)
+    {
+        const BatchFrame& x = fr[i];
+        if (x.done || x.reader.component_count() < 2 || x.reader.scan_interleave_mode() != 0 || x.reader.scan_component_count() != 1)
+            continue;
+        if (probe.empty())
+            probe = fr; // (readers, windows and cursors of every frame; only the planned ones are touched)
+        Plan p;
+        p.frame = i;
+        try
+        { // every plane must fit behind the first (the rounds raise the error where it belongs otherwise)
+            const auto [row, stride] = row_and_stride(x.reader, b.to.dests[i].stride);
+            if (stride < row || b.to.dests[i].capacity_bytes <
+                                    checked_mul(checked_mul(stride, x.reader.frame_info().height), x.reader.component_count()) - (stride - row))
                 continue;
-            if (probe.empty())
-                probe = fr; // (readers, windows and cursors of every frame; only the planned ones are touched)
-            Plan p;
-            p.frame = i;
+            p.scans.push_back(scan_desc_for(b, i, probe[i]));
+        }
+        catch (const error&)
+        {
+            continue;
+        }
+        p.starts.push_back(x.cursor);
+        plans.push_back(std::move(p));
+    }
+    dev::DeviceBuffer d_search, d_found;
+    dev::PinnedBuffer h_search, h_found;
+    for (uint32_t c = 1; !plans.empty(); ++c)
+    {
+        std::vector<uint32_t> need; // plans whose frame has a scan c
+        for (uint32_t k = 0; k < plans.size(); ++k)
+            if (plans[k].ok && probe[plans[k].frame].reader.component_count() > c)
+                need.push_back(k);
+        if (need.empty())
+            break;
+        const size_t n = need.size();
+        auto* search = static_cast<MarkerSearch*>(h_search.ensure(sizeof(MarkerSearch) * n));
+        auto* found = static_cast<unsigned long long*>(h_found.ensure(sizeof(unsigned long long) * n));
+        for (size_t q = 0; q < n; ++q)
+        {
+            const uint32_t i = plans[need[q]].frame;
+            search[q] = MarkerSearch{win.offset_of(i) + plans[need[q]].starts.back(), win.offset_of(i) + win.sizes[i]};
+        }
+        d_search.ensure(sizeof(MarkerSearch) * n);
+        d_found.ensure(sizeof(unsigned long long) * n);
+        hip_check(hipMemcpyAsync(d_search.as<MarkerSearch>(), search, sizeof(MarkerSearch) * n, hipMemcpyHostToDevice, stream));
+        dev::launch_find_scan_end(win.slots, d_search.as<const MarkerSearch>(), d_found.as<unsigned long long>(), static_cast<uint32_t>(n), stream);
+        hip_check(hipMemcpyAsync(found, d_found.as<unsigned long long>(), sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, stream));
+        hip_check(hipStreamSynchronize(stream));
+        std::vector<uint32_t> which;
+        std::vector<size_t> bases;
+        for (size_t q = 0; q < n; ++q)
+        {
+            Plan& p = plans[need[q]];
+            if (found[q] == kNoMarker)
+            {
+                p.ok = false;
+                continue;
+            }
+            p.marker_at.push_back(static_cast<size_t>(found[q] - win.offset_of(p.frame)));
+            which.push_back(p.frame);
+            bases.push_back(p.marker_at.back());
+        }
+        win.parse_behind_scans(probe, which, bases, std::vector<uint8_t>(which.size(), 0));
+        for (size_t q = 0; q < n; ++q)
+        {
+            Plan& p = plans[need[q]];
+            if (!p.ok)
+                continue;
+            BatchFrame& y = probe[p.frame];
+            y.plane_offset += p.scans.back().pixel_stride * p.scans.back().height; // (past the plane of the scan before)
+            if (y.done || y.reader.scan_interleave_mode() != 0 || y.reader.scan_component_count() != 1)
+            {
+                p.ok = false;
+                continue;
+            }
             try
-            { // every plane must fit behind the first (the rounds raise the error where it belongs otherwise)
-                const charls_frame_info& f = x.reader.frame_info();
-                const size_t row = static_cast<size_t>(f.width) * bytes_per_sample(f.bits_per_sample);
-                const size_t stride = to.dests[i].stride == 0 ? row : to.dests[i].stride;
-                if (stride < row || to.dests[i].capacity_bytes < checked_mul(checked_mul(stride, f.height), x.reader.component_count()) - (stride - row))
-                    continue;
-                p.scans.push_back(scan_desc(i, probe[i], scratch_total));
+            {
+                p.scans.push_back(scan_desc_for(b, p.frame, y));
+                p.starts.push_back(y.cursor);
             }
             catch (const error&)
             {
-                continue;
-            }
-            p.starts.push_back(x.cursor);
-            plans.push_back(std::move(p));
-        }
-        dev::DeviceBuffer d_search, d_found;
-        dev::PinnedBuffer h_search, h_found;
-        for (uint32_t c = 1; !plans.empty(); ++c)
-        {
-            std::vector<uint32_t> need; // plans whose frame has a scan c
-            for (uint32_t k = 0; k < plans.size(); ++k)
-                if (plans[k].ok && probe[plans[k].frame].reader.component_count() > c)
-                    need.push_back(k);
-            if (need.empty())
-                break;
-            const size_t n = need.size();
-            auto* search = static_cast<MarkerSearch*>(h_search.ensure(sizeof(MarkerSearch) * n));
-            auto* found = static_cast<unsigned long long*>(h_found.ensure(sizeof(unsigned long long) * n));
-            for (size_t q = 0; q < n; ++q)
-            {
-                const uint32_t i = plans[need[q]].frame;
-                search[q] = MarkerSearch{stream_at[i] + plans[need[q]].starts.back(), stream_at[i] + sizes[i]};
-            }
-            d_search.ensure(sizeof(MarkerSearch) * n);
-            d_found.ensure(sizeof(unsigned long long) * n);
-            hip_check(hipMemcpyAsync(d_search.as<MarkerSearch>(), search, sizeof(MarkerSearch) * n, hipMemcpyHostToDevice, stream));
-            dev::launch_find_scan_end(slots, d_search.as<const MarkerSearch>(), d_found.as<unsigned long long>(), static_cast<uint32_t>(n), stream);
-            hip_check(hipMemcpyAsync(found, d_found.as<unsigned long long>(), sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, stream));
-            hip_check(hipStreamSynchronize(stream));
-            std::vector<uint32_t> which;
-            std::vector<size_t> bases;
-            for (size_t q = 0; q < n; ++q)
-            {
-                Plan& p = plans[need[q]];
-                if (found[q] == kNoMarker)
-                {
-                    p.ok = false;
-                    continue;
-                }
-                p.marker_at.push_back(static_cast<size_t>(found[q] - stream_at[p.frame]));
-                which.push_back(p.frame);
-                bases.push_back(p.marker_at.back());
-            }
-            fetch_many(probe, which, bases);
-            for (size_t q = 0; q < n; ++q)
-            {
-                Plan& p = plans[need[q]];
-                if (!p.ok)
-                    continue;
-                Frame& y = probe[p.frame];
-                const charls_frame_info f = y.reader.frame_info();
-                const size_t row = static_cast<size_t>(f.width) * bytes_per_sample(f.bits_per_sample);
-                y.plane_offset += (to.dests[p.frame].stride ? to.dests[p.frame].stride : row) * f.height;
-                parse(probe, p.frame, [&](Frame& z) {
-                    z.reader.continue_on_window(z.window.data(), z.window.size());
-                    z.reader.read_next_start_of_scan();
-                    z.cursor = z.window_base + static_cast<size_t>(z.reader.position() - z.window.data());
-                });
-                if (y.done || y.reader.scan_interleave_mode() != 0 || y.reader.scan_component_count() != 1)
-                {
-                    p.ok = false;
-                    continue;
-                }
-                try
-                {
-                    p.scans.push_back(scan_desc(p.frame, y, scratch_total));
-                    p.starts.push_back(y.cursor);
-                }
-                catch (const error&)
-                {
-                    p.ok = false;
-                }
-            }
-        }
-        descs.clear();
-        std::vector<uint32_t> tags; // plan << 8 | component
-        for (uint32_t k = 0; k < plans.size(); ++k)
-        {
-            Plan& p = plans[k];
-            p.ok = p.ok && p.scans.size() == probe[p.frame].reader.component_count() && p.scans.size() < 256;
-            for (uint32_t c = 0; p.ok && c < p.scans.size(); ++c)
-            {
-                descs.push_back(p.scans[c]);
-                tags.push_back((k << 8) | c);
-            }
-        }
-        if (!descs.empty())
-        {
-            run_scans(tags, scratch_total);
-            std::vector<std::vector<size_t>> used(plans.size());
-            for (Plan& p : plans)
-                used[&p - plans.data()].assign(p.scans.size(), 0);
-            for (uint32_t k = 0; k < tags.size(); ++k)
-            {
-                Plan& p = plans[tags[k] >> 8];
-                const uint32_t c = tags[k] & 0xFFu;
-                if (results[k].errc != kOk)
-                    p.ok = false;
-                used[tags[k] >> 8][c] = static_cast<size_t>(results[k].bytes);
-            }
-            std::vector<uint32_t> which;
-            std::vector<size_t> bases;
-            for (uint32_t k = 0; k < plans.size(); ++k)
-            {
-                Plan& p = plans[k];
-                for (uint32_t c = 0; p.ok && c + 1 < p.scans.size(); ++c)
-                    p.ok = p.starts[c] + used[k][c] == p.marker_at[c]; // the scan ends exactly at the marker found behind it
-                if (!p.ok)
-                    continue;
-                probe[p.frame].cursor = p.starts.back() + used[k].back();
-                which.push_back(p.frame);
-                bases.push_back(probe[p.frame].cursor);
-            }
-            fetch_many(probe, which, bases);
-            for (Plan& p : plans)
-            {
-                if (!p.ok)
-                    continue;
-                parse(probe, p.frame, [&](Frame& z) {
-                    z.reader.continue_on_window(z.window.data(), z.window.size());
-                    z.reader.read_end_of_image();
-                    z.cursor = z.window_base + static_cast<size_t>(z.reader.position() - z.window.data());
-                });
-                Frame& y = probe[p.frame];
-                if (y.errc != CHARLS_JPEGLS_ERRC_SUCCESS)
-                    continue; // (the rounds decode it again and report this)
-                report_params(fr[p.frame], p.frame);
-                y.decoded_components = static_cast<uint32_t>(p.scans.size());
-                y.done = true;
-                fr[p.frame] = std::move(y);
+                p.ok = false;
             }
         }
     }
+    std::vector<ScanDesc> descs;
+    for (Plan& p : plans)
+    {
+        p.ok = p.ok && p.scans.size() == probe[p.frame].reader.component_count();
+        if (!p.ok)
+            continue;
+        p.first_desc = descs.size();
+        descs.insert(descs.end(), p.scans.begin(), p.scans.end());
+    }
+    if (descs.empty())
+        return;
+    std::vector<ScanResult> results;
+    b.launcher.run(descs, results);
+    std::vector<uint32_t> which;
+    std::vector<size_t> bases;
+    for (Plan& p : plans)
+    {
+        if (!p.ok)
+            continue;
+        for (uint32_t c = 0; c < p.scans.size(); ++c)
+        {
+            const ScanResult& r = results[p.first_desc + c];
+            p.ok = p.ok && r.errc == kOk;
+            p.used.push_back(static_cast<size_t>(r.bytes));
+        }
+        for (uint32_t c = 0; p.ok && c + 1 < p.scans.size(); ++c)
+            p.ok = p.starts[c] + p.used[c] == p.marker_at[c]; // the scan ends exactly at the marker found behind it
+        if (!p.ok)
+            continue;
+        probe[p.frame].cursor = p.starts.back() + p.used.back();
+        which.push_back(p.frame);
+        bases.push_back(probe[p.frame].cursor);
+    }
+    win.parse_behind_scans(probe, which, bases, std::vector<uint8_t>(which.size(), 1));
+    for (Plan& p : plans)
+    {
+        if (!p.ok)
+            continue;
+        BatchFrame& y = probe[p.frame];
+        if (y.errc != CHARLS_JPEGLS_ERRC_SUCCESS)
+            continue; // (the rounds decode it again and report this)
+        report_params(b, fr[p.frame], p.frame);
+        y.decoded_components = static_cast<uint32_t>(p.scans.size());
+        y.done = true;
+        fr[p.frame] = std::move(y);
+    }
+}
 
-
+// Scan by scan: one round decodes the next scan of every frame that has one, then parses what follows it.
+void decode_by_rounds(BatchDecode& b)
+{
+    std::vector<BatchFrame>& fr = b.win.fr;
+    std::vector<ScanDesc> descs;
+    std::vector<ScanResult> results;
+    std::vector<uint32_t> active;
     for (;;)
     {
         active.clear();
         descs.clear();
-        size_t scratch_total = 0;
-        for (uint32_t i = 0; i < frame_count; ++i)
+        for (uint32_t i = 0; i < fr.size(); ++i)
         {
-            Frame& x = fr[i];
+            BatchFrame& x = fr[i];
             if (x.done)
                 continue;
             try
             {
-                const ScanDesc d = scan_desc(i, x, scratch_total);
-                report_params(x, i);
+                const ScanDesc d = scan_desc_for(b, i, x);
+                report_params(b, x, i);
                 descs.push_back(d);
                 active.push_back(i);
             }
@@ -883,65 +676,66 @@ void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, cons
         }
         if (active.empty())
             break;
-        const uint32_t n = static_cast<uint32_t>(active.size());
-        run_scans(active, scratch_total);
+        b.launcher.run(descs, results);
 
-        // advance every frame past its scan; fetch the bytes that follow (next SOS or EOI)
+        // advance every frame past its scan; parse the bytes that follow (next SOS or EOI)
+        std::vector<uint32_t> which;
+        std::vector<size_t> bases;
+        std::vector<uint8_t> last;
+        for (uint32_t k = 0; k < active.size(); ++k)
         {
-            std::vector<uint32_t> which;
-            std::vector<size_t> bases;
-            which.reserve(n);
-            bases.reserve(n);
-            for (uint32_t k = 0; k < n; ++k)
+            BatchFrame& x = fr[active[k]];
+            if (results[k].errc != kOk)
             {
-                Frame& x = fr[active[k]];
-                if (results[k].errc != kOk)
-                {
-                    x.errc = static_cast<charls_jpegls_errc>(results[k].errc);
-                    x.done = true;
-                    continue;
-                }
-                x.cursor += results[k].bytes;
-                which.push_back(active[k]);
-                bases.push_back(x.cursor);
-            }
-            fetch_many(fr, which, bases);
-        }
-        for (uint32_t k = 0; k < n; ++k)
-        {
-            const uint32_t i = active[k];
-            Frame& x = fr[i];
-            if (x.done)
-                continue;
-            const charls_frame_info f = x.reader.frame_info();
-            const uint32_t nc = x.reader.scan_component_count();
-            const int32_t ilv = x.reader.scan_interleave_mode();
-            x.decoded_components += nc;
-            const bool last = x.decoded_components == x.reader.component_count();
-            if (!last)
-            {
-                const size_t row = (ilv == 0 ? 1u : nc) * static_cast<size_t>(f.width) * bytes_per_sample(f.bits_per_sample);
-                const size_t stride = to.dests[i].stride ? to.dests[i].stride : row;
-                x.plane_offset += stride * f.height;
-            }
-            parse(fr, i, [&](Frame& y) {
-                // continue the same reader on the freshly fetched window
-                y.reader.continue_on_window(y.window.data(), y.window.size());
-                if (last)
-                    y.reader.read_end_of_image();
-                else
-                    y.reader.read_next_start_of_scan();
-                y.cursor = y.window_base + static_cast<size_t>(y.reader.position() - y.window.data());
-            });
-            if (last)
+                x.errc = static_cast<charls_jpegls_errc>(results[k].errc);
                 x.done = true;
+                continue;
+            }
+            x.cursor += results[k].bytes;
+            x.decoded_components += x.reader.scan_component_count();
+            const bool end = x.decoded_components == x.reader.component_count();
+            if (!end)
+                x.plane_offset += descs[k].pixel_stride * descs[k].height;
+            which.push_back(active[k]);
+            bases.push_back(x.cursor);
+            last.push_back(end ? 1 : 0);
         }
+        b.win.parse_behind_scans(fr, which, bases, last);
+        for (size_t k = 0; k < which.size(); ++k)
+            if (last[k])
+                fr[which[k]].done = true;
     }
+}
+
+} // namespace
+
+// The batch decoder behind charls_amd_decode_batch_device (slots: stream_at[i] = i * pitch),
+// charls_amd_decode_batch_device_packed (batch_packed.cpp: stream_at = the caller's offset table) and the calls of part 2e
+// (batch_ragged.cpp: a destination per frame, or none -- the probe): frame i's stream is the sizes[i] bytes at
+// d_streams + stream_at[i] and goes to to.dests[i].  frame_count >= 1, the pointers are checked by the entry points.
+void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, const uint64_t* stream_at, const uint64_t* sizes,
+                               const BatchDests& to, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs,
+                               void* hip_stream)
+{
+    dev::require_device();
+    auto stream = static_cast<hipStream_t>(hip_stream);
+    const bool probing = to.dests == nullptr;
+    StreamWindows win(frame_count, d_streams, stream_at, sizes, stream);
+    win.read_headers(!probing);
+    if (probing)
+        return probe_frames(win, to, params_out, errcs);
+    if (to.ragged)
+        check_ragged_dests(win, to);
+    DecodeLauncher launcher(stream);
+    BatchDecode b{win, launcher, to, params_out, UINT32_MAX};
+    if (knobs::get_or(knobs::kBatchRounds, 0) == 0)
+        decode_planar_in_one_launch(b);
+    decode_by_rounds(b);
     for (uint32_t i = 0; i < frame_count; ++i)
-        errcs[i] = fr[i].errc;
+        errcs[i] = win.fr[i].errc;
     dev::Timings& t = dev::last_timings();
-    t.values[0] = scan_ms;
-    t.values[1] = scan_ms;
+    t.values[0] = launcher.gpu_ms();
+    t.values[1] = launcher.gpu_ms();
     t.count = 2;
 }
 
@@ -959,15 +753,7 @@ try
     check_pointer(d_streams);
     check_pointer(d_frames);
     dev::require_device();
-    if (stream_pitch_bytes == 0)
-        raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
-    std::vector<uint64_t> stream_at(frame_count);
-    for (uint32_t i = 0; i < frame_count; ++i)
-    {
-        if (sizes[i] > stream_pitch_bytes)
-            raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
-        stream_at[i] = static_cast<uint64_t>(i) * stream_pitch_bytes;
-    }
+    const std::vector<uint64_t> stream_at = slot_offsets(frame_count, stream_pitch_bytes, sizes);
     decode_batch_streams(frame_count, d_streams, stream_at.data(), sizes, d_frames, frame_pitch_bytes, stride_arg, params_out, errcs,
                          hip_stream);
     return CHARLS_JPEGLS_ERRC_SUCCESS;

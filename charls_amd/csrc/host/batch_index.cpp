@@ -25,14 +25,12 @@
 #include "preset.h"
 #include "seek_index.h"
 #include "stream_reader.h"
-#include "window_fetch.h"
+#include "stream_windows.h"
 
 using namespace jls;
 using dev::hip_check;
 
 namespace {
-
-constexpr size_t kWindow = 2048;
 
 enum : int
 { // dev::seek_arena
@@ -46,38 +44,6 @@ enum : int
 
 // GPU time of the seek launches and of the hash launches of the running call (charls_amd_last_timings [0] and [1]).
 thread_local double t_seek_ms = 0, t_hash_ms = 0;
-class GpuClock
-{
-public:
-    GpuClock(hipStream_t stream, double& total) : stream_(stream), total_(total)
-    {
-        hip_check(hipEventCreate(&a_));
-        if (hipEventCreate(&b_) != hipSuccess)
-        {
-            (void)hipEventDestroy(a_);
-            raise(CHARLS_AMD_ERRC_DEVICE_FAILURE);
-        }
-        (void)hipEventRecord(a_, stream_);
-    }
-    GpuClock(const GpuClock&) = delete;
-    GpuClock& operator=(const GpuClock&) = delete;
-    void stop() { (void)hipEventRecord(b_, stream_); } // before the synchronisation that follows the launch
-    ~GpuClock()
-    { // (behind that synchronisation)
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, a_, b_) == hipSuccess)
-            total_ += ms;
-        else
-            (void)hipGetLastError();
-        (void)hipEventDestroy(a_);
-        (void)hipEventDestroy(b_);
-    }
-
-private:
-    hipEvent_t a_{}, b_{};
-    hipStream_t stream_;
-    double& total_;
-};
 void timings_begin() noexcept
 {
     t_seek_ms = t_hash_ms = 0;
@@ -90,194 +56,21 @@ void timings_end() noexcept
     t.count = 2;
 }
 
-struct Frame
-{
-    StreamReader reader;
-    std::vector<uint8_t> window; // host copy of [window_base, window_base + window.size())
-    size_t window_base{};
-    size_t cursor{};       // absolute offset of the next unparsed byte
-    size_t plane_offset{}; // destination offset of the next scan
-    uint32_t decoded_components{};
-    charls_jpegls_errc errc{};
-    bool done{};
-};
-
-// The streams of a call and the host's windows into them: charls_amd_decode_batch_device's way of parsing.
-class Streams
-{
-public:
-    Streams(uint32_t count, const void* d_streams, size_t pitch, const uint64_t* sizes_arg, hipStream_t s)
-        : slots(static_cast<const uint8_t*>(d_streams)), stream_pitch(pitch), sizes(sizes_arg), stream(s), fr(count)
-    {
-        if (pitch == 0)
-            raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
-        for (uint32_t i = 0; i < count; ++i)
-            if (sizes[i] > pitch)
-                raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
-    }
-
-    void fetch(Frame& x, uint32_t i, size_t base, size_t bytes)
-    {
-        const size_t avail = base < sizes[i] ? static_cast<size_t>(sizes[i]) - base : 0;
-        const size_t n = std::min(bytes, avail);
-        x.window.resize(n);
-        x.window_base = base;
-        if (n)
-            hip_check(hipMemcpyAsync(x.window.data(), slots + i * stream_pitch + base, n, hipMemcpyDeviceToHost, stream));
-    }
-    // one gather on the device, one copy (bases[k] is the offset of frame which[k]'s window)
-    void fetch_many(std::vector<Frame>& set, const std::vector<uint32_t>& which, const std::vector<size_t>& bases)
-    {
-        const size_t n = which.size();
-        if (n == 0)
-            return;
-        auto* specs = static_cast<WindowSpec*>(h_specs_.ensure(sizeof(WindowSpec) * n));
-        for (size_t k = 0; k < n; ++k)
-        {
-            const uint32_t i = which[k];
-            const size_t avail = bases[k] < sizes[i] ? static_cast<size_t>(sizes[i]) - bases[k] : 0;
-            specs[k] = WindowSpec{static_cast<uint64_t>(i) * stream_pitch + bases[k], static_cast<uint32_t>(std::min(kWindow, avail)), 0};
-        }
-        d_specs_.ensure(sizeof(WindowSpec) * n);
-        d_windows_.ensure(kWindow * n);
-        auto* staged = static_cast<uint8_t*>(h_windows_.ensure(kWindow * n));
-        hip_check(hipMemcpyAsync(d_specs_.as<WindowSpec>(), specs, sizeof(WindowSpec) * n, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(gather_windows, dim3(static_cast<uint32_t>(n)), dim3(256), 0, stream, slots, d_specs_.as<const WindowSpec>(),
-                           d_windows_.as<uint8_t>(), static_cast<uint32_t>(kWindow));
-        hip_check(hipGetLastError());
-        hip_check(hipMemcpyAsync(staged, d_windows_.as<uint8_t>(), kWindow * n, hipMemcpyDeviceToHost, stream));
-        hip_check(hipStreamSynchronize(stream));
-        for (size_t k = 0; k < n; ++k)
-        {
-            Frame& x = set[which[k]];
-            x.window.assign(staged + k * kWindow, staged + k * kWindow + specs[k].bytes);
-            x.window_base = bases[k];
-        }
-    }
-    // A parse that runs off the end of the window while the stream has more bytes is retried with a larger window.
-    template <typename Body>
-    void parse(std::vector<Frame>& set, uint32_t i, Body&& body)
-    {
-        Frame& x = set[i];
-        size_t want = kWindow;
-        const StreamReader snapshot = x.reader;
-        for (;;)
-        {
-            try
-            {
-                body(x);
-                x.errc = CHARLS_JPEGLS_ERRC_SUCCESS;
-                return;
-            }
-            catch (const error& e)
-            {
-                const bool truncated = x.window_base + x.window.size() < sizes[i];
-                if (!truncated || (e.code != CHARLS_JPEGLS_ERRC_NEED_MORE_DATA && e.code != CHARLS_JPEGLS_ERRC_INVALID_MARKER_SEGMENT_SIZE &&
-                                   e.code != CHARLS_JPEGLS_ERRC_DEFINE_NUMBER_OF_LINES_MARKER_NOT_FOUND))
-                {
-                    x.errc = e.code;
-                    x.done = true;
-                    return;
-                }
-            }
-            want *= 8;
-            fetch(x, i, x.window_base, want);
-            hip_check(hipStreamSynchronize(stream));
-            x.reader = snapshot;
-        }
-    }
-    void read_headers()
-    {
-        const uint32_t n = static_cast<uint32_t>(fr.size());
-        std::vector<uint32_t> all(n);
-        for (uint32_t i = 0; i < n; ++i)
-            all[i] = i;
-        fetch_many(fr, all, std::vector<size_t>(n, 0));
-        for (uint32_t i = 0; i < n; ++i)
-            parse(fr, i, [&](Frame& x) {
-                x.reader.set_source(x.window.data(), x.window.size());
-                x.reader.read_header();
-                if (x.reader.end_of_image())
-                    raise(CHARLS_JPEGLS_ERRC_INVALID_OPERATION); // abbreviated table stream: nothing to decode
-                x.cursor = x.window_base + static_cast<size_t>(x.reader.position() - x.window.data());
-            });
-    }
-    // The frames `which` stand at `bases` (behind a scan): what follows is parsed on fresh windows, the next SOS, or the end
-    // of the image where last[k].
-    void parse_behind_scans(std::vector<Frame>& set, const std::vector<uint32_t>& which, const std::vector<size_t>& bases,
-                            const std::vector<uint8_t>& last)
-    {
-        fetch_many(set, which, bases);
-        for (size_t k = 0; k < which.size(); ++k)
-        {
-            const bool end = last[k] != 0;
-            parse(set, which[k], [&](Frame& y) {
-                y.reader.continue_on_window(y.window.data(), y.window.size());
-                if (end)
-                    y.reader.read_end_of_image();
-                else
-                    y.reader.read_next_start_of_scan();
-                y.cursor = y.window_base + static_cast<size_t>(y.reader.position() - y.window.data());
-            });
-        }
-    }
-
-    const uint8_t* slots;
-    size_t stream_pitch;
-    const uint64_t* sizes;
-    hipStream_t stream;
-    std::vector<Frame> fr;
-
-private:
-    dev::DeviceBuffer d_specs_, d_windows_;
-    dev::PinnedBuffer h_specs_, h_windows_;
-};
-
-ScanDesc desc_from(const ScanSpec& s) noexcept
-{
-    ScanDesc d{};
-    d.width = s.width;
-    d.height = s.height;
-    d.components = s.components;
-    d.interleave_mode = s.interleave_mode;
-    d.bits_per_sample = s.bits_per_sample;
-    d.near_lossless = s.near_lossless;
-    d.color_transformation = s.color_transformation;
-    d.t1 = s.pc.threshold1;
-    d.t2 = s.pc.threshold2;
-    d.t3 = s.pc.threshold3;
-    d.reset = static_cast<uint8_t>(s.pc.reset_value);
-    d.restart_interval = s.restart_interval;
-    return d;
-}
-
-size_t planes_of(const ScanSpec& s) noexcept
-{
-    return s.interleave_mode == 0 ? 1u : static_cast<size_t>(s.components);
-}
-size_t row_bytes_of(const ScanSpec& s) noexcept
-{
-    return planes_of(s) * s.width * bytes_per_sample(s.bits_per_sample);
-}
-
 // The scan whose header x's reader has read, decoding to `frames + i * frame_pitch` with the checks
 // charls_amd_decode_batch_device makes (stride, extent).  No line scratch.
-ScanDesc frame_scan_desc(const Streams& s, uint32_t i, const Frame& x, uint8_t* frames, size_t frame_pitch, uint32_t stride_arg)
+ScanDesc frame_scan_desc(const StreamWindows& s, uint32_t i, const BatchFrame& x, uint8_t* frames, size_t frame_pitch, uint32_t stride_arg)
 {
     const ScanSpec spec = scan_spec_of(x.reader);
-    const size_t row = row_bytes_of(spec);
-    size_t stride = stride_arg;
-    if (stride == 0)
-        stride = row;
-    else if (stride < row)
+    const auto [row, stride] = row_and_stride(x.reader, stride_arg);
+    if (stride < row)
         raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_STRIDE);
     const size_t need = stride * spec.height - (stride - row); // (a scan of ILV_NONE is one component)
     if (frame_pitch < x.plane_offset + need)
         raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
-    ScanDesc d = desc_from(spec);
+    ScanDesc d = desc_of(spec);
     d.pixels = frames + i * frame_pitch + x.plane_offset;
     d.pixel_stride = stride;
-    d.stream = const_cast<uint8_t*>(s.slots) + i * s.stream_pitch + x.cursor;
+    d.stream = s.stream_ptr(i, x.cursor);
     d.stream_capacity = s.sizes[i] - x.cursor;
     d.line_scratch = nullptr; // (the seek kernels keep their lines in LDS)
     return d;
@@ -349,12 +142,14 @@ void run_emit(const std::vector<ScanDesc>& descs, const std::vector<size_t>& poi
             std::vector<ScanResult> got(count);
             hip_check(hipMemcpyAsync(d_descs, pass.data(), sizeof(ScanDesc) * count, hipMemcpyHostToDevice, stream));
             {
-                GpuClock clock(stream, t_seek_ms);
+                EventTimer clock(stream, true);
+                clock.start();
                 dev::launch_seek_emit(descs[proto], d_descs, d_results, count, d_points, stride, lines, stream);
                 clock.stop();
                 add_index_counters(0, 0, 0, 1);
                 hip_check(hipMemcpyAsync(got.data(), d_results, sizeof(ScanResult) * count, hipMemcpyDeviceToHost, stream));
                 hip_check(hipStreamSynchronize(stream));
+                t_seek_ms += clock.ms();
             }
             for (uint32_t k = 0; k < count; ++k)
             {
@@ -435,12 +230,14 @@ void run_resume(std::vector<ResumeScan>& scans, hipStream_t stream)
         {
             hip_check(hipMemcpyAsync(d_descs, pass.data(), sizeof(ScanDesc) * count, hipMemcpyHostToDevice, stream));
             hip_check(hipMemcpyAsync(d_work, work.data(), sizeof(seek::SeekWork) * items, hipMemcpyHostToDevice, stream));
-            GpuClock clock(stream, t_seek_ms);
+            EventTimer clock(stream, true);
+            clock.start();
             dev::launch_seek_resume(descs[proto], d_descs, d_work, d_results, static_cast<uint32_t>(items), d_points, stream);
             clock.stop();
             add_index_counters(0, items, 0, 1);
             hip_check(hipMemcpyAsync(got.data(), d_results, sizeof(ScanResult) * items, hipMemcpyDeviceToHost, stream));
             hip_check(hipStreamSynchronize(stream));
+            t_seek_ms += clock.ms();
         }
         hip_check(hipStreamSynchronize(stream));
         size_t item = 0;
@@ -455,7 +252,7 @@ void run_resume(std::vector<ResumeScan>& scans, hipStream_t stream)
 }
 
 // segment_hash of the bytes [offset, offset + bytes) of the slots, job by job, on the device.
-std::vector<uint64_t> device_hashes(const Streams& s, const std::vector<seek::HashJob>& jobs)
+std::vector<uint64_t> device_hashes(const StreamWindows& s, const std::vector<seek::HashJob>& jobs)
 {
     const size_t n = jobs.size();
     std::vector<uint64_t> out(n);
@@ -464,72 +261,22 @@ std::vector<uint64_t> device_hashes(const Streams& s, const std::vector<seek::Ha
     const size_t jobs_bytes = (sizeof(seek::HashJob) * n + 15) & ~size_t{15};
     auto* area = static_cast<uint8_t*>(dev::seek_arena(kArenaHash).ensure(dev::with_headroom(jobs_bytes + sizeof(uint64_t) * n)));
     hip_check(hipMemcpyAsync(area, jobs.data(), sizeof(seek::HashJob) * n, hipMemcpyHostToDevice, s.stream));
-    GpuClock clock(s.stream, t_hash_ms);
+    EventTimer clock(s.stream, true);
+    clock.start();
     dev::launch_segment_hash(s.slots, reinterpret_cast<const seek::HashJob*>(area), reinterpret_cast<uint64_t*>(area + jobs_bytes),
                              static_cast<uint32_t>(n), s.stream);
     clock.stop();
     hip_check(hipMemcpyAsync(out.data(), area + jobs_bytes, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, s.stream));
     hip_check(hipStreamSynchronize(s.stream));
+    t_hash_ms += clock.ms();
     return out;
-}
-
-// The ordinary launches for one round of scans that get no seek points (the build call needs every scan's length, which
-// charls_amd_decode_batch_device does not report): as its run_scans.
-void run_ordinary(std::vector<ScanDesc>& descs, std::vector<ScanResult>& results, hipStream_t stream)
-{
-    const uint32_t n = static_cast<uint32_t>(descs.size());
-    results.assign(n, ScanResult{});
-    if (n == 0)
-        return;
-    dev::DeviceBuffer d_descs, d_results, d_scratch;
-    size_t scratch_total = 0;
-    std::vector<size_t> scratch_at(n);
-    for (uint32_t k = 0; k < n; ++k)
-    {
-        scratch_at[k] = scratch_total;
-        scratch_total += dev::line_scratch_samples(descs[k].width, descs[k].interleave_mode, descs[k].components) * sizeof(uint16_t);
-        scratch_total = (scratch_total + 255) & ~size_t{255};
-    }
-    auto* scratch = static_cast<uint8_t*>(d_scratch.ensure(scratch_total));
-    std::vector<uint32_t> order(n);
-    for (uint32_t k = 0; k < n; ++k)
-    {
-        order[k] = k;
-        descs[k].line_scratch = reinterpret_cast<uint16_t*>(scratch + scratch_at[k]);
-    }
-    std::stable_sort(order.begin(), order.end(),
-                     [&](uint32_t a, uint32_t b) { return dev::decode_launch_key(descs[a]) < dev::decode_launch_key(descs[b]); });
-    std::vector<ScanDesc> sorted(n);
-    for (uint32_t k = 0; k < n; ++k)
-        sorted[k] = descs[order[k]];
-    d_descs.ensure(sizeof(ScanDesc) * n);
-    d_results.ensure(sizeof(ScanResult) * n);
-    hip_check(hipMemcpyAsync(d_descs.as<ScanDesc>(), sorted.data(), sizeof(ScanDesc) * n, hipMemcpyHostToDevice, stream));
-    for (uint32_t first = 0; first < n;)
-    {
-        uint32_t last = first + 1;
-        while (last < n && dev::decode_launch_key(sorted[last]) == dev::decode_launch_key(sorted[first]))
-            ++last;
-        dev::launch_decode(sorted[first], d_descs.as<ScanDesc>() + first, d_results.as<ScanResult>() + first, last - first, stream);
-        first = last;
-    }
-    std::vector<ScanResult> got(n);
-    hip_check(hipMemcpyAsync(got.data(), d_results.as<ScanResult>(), sizeof(ScanResult) * n, hipMemcpyDeviceToHost, stream));
-    hip_check(hipStreamSynchronize(stream));
-    for (uint32_t k = 0; k < n; ++k)
-        results[order[k]] = got[k];
-}
-
-charls_amd_codec_params params_of(const StreamReader& r)
-{
-    return charls_amd_codec_params{r.frame_info(), r.parameters().near_lossless, r.scan_interleave_mode(), r.parameters().transformation,
-                                   r.preset_coding_parameters(), 0, r.parameters().restart_interval};
 }
 
 // Every run of frames marked in `ordinary` through charls_amd_decode_batch_device; params_out as that call documents it
 // (params_from: the lowest frame whose parameters it holds so far).
-charls_jpegls_errc decode_ordinary(const Streams& s, const std::vector<uint8_t>& ordinary, uint8_t* frames, size_t frame_pitch,
-                                   uint32_t stride, charls_amd_codec_params* params_out, uint32_t& params_from, charls_jpegls_errc* errcs)
+charls_jpegls_errc decode_ordinary(const StreamWindows& s, size_t stream_pitch, const std::vector<uint8_t>& ordinary, uint8_t* frames,
+                                   size_t frame_pitch, uint32_t stride, charls_amd_codec_params* params_out, uint32_t& params_from,
+                                   charls_jpegls_errc* errcs)
 {
     const uint32_t n = static_cast<uint32_t>(ordinary.size());
     for (uint32_t i = 0; i < n;)
@@ -544,8 +291,8 @@ charls_jpegls_errc decode_ordinary(const Streams& s, const std::vector<uint8_t>&
             ++last;
         charls_amd_codec_params got{};
         const charls_jpegls_errc rc =
-            charls_amd_decode_batch_device(last - i, s.slots + i * s.stream_pitch, s.stream_pitch, s.sizes + i, frames + i * frame_pitch,
-                                           frame_pitch, stride, &got, errcs + i, s.stream);
+            charls_amd_decode_batch_device(last - i, s.slots + s.offset_of(i), stream_pitch, s.sizes + i, frames + i * frame_pitch, frame_pitch,
+                                           stride, &got, errcs + i, s.stream);
         if (rc != CHARLS_JPEGLS_ERRC_SUCCESS)
             return rc;
         if (params_out && got.frame_info.width != 0 && i < params_from)
@@ -559,13 +306,13 @@ charls_jpegls_errc decode_ordinary(const Streams& s, const std::vector<uint8_t>&
 }
 
 // set_index for every frame that has one: parsed[i] (empty scans: none), errors to the frame.
-void parse_indexes(Streams& s, const void* indexes, size_t index_pitch, const uint64_t* index_sizes, std::vector<SeekIndex>& parsed)
+void parse_indexes(StreamWindows& s, const void* indexes, size_t index_pitch, const uint64_t* index_sizes, std::vector<SeekIndex>& parsed)
 {
     const uint32_t n = static_cast<uint32_t>(s.fr.size());
     parsed.assign(n, SeekIndex{});
     for (uint32_t i = 0; i < n; ++i)
     {
-        Frame& x = s.fr[i];
+        BatchFrame& x = s.fr[i];
         if (x.done || index_sizes[i] == 0)
             continue;
         try
@@ -645,9 +392,10 @@ try
     dev::require_device();
     auto stream = static_cast<hipStream_t>(hip_stream);
     auto* frames = static_cast<uint8_t*>(d_frames);
-    Streams s(frame_count, d_streams, stream_pitch_bytes, sizes, stream);
+    const std::vector<uint64_t> stream_at = slot_offsets(frame_count, stream_pitch_bytes, sizes);
+    StreamWindows s(frame_count, d_streams, stream_at.data(), sizes, stream);
     timings_begin();
-    s.read_headers();
+    s.read_headers(true);
 
     struct Build
     {
@@ -658,7 +406,7 @@ try
     std::vector<Build> builds(frame_count);
     for (uint32_t i = 0; i < frame_count; ++i)
     {
-        Frame& x = s.fr[i];
+        BatchFrame& x = s.fr[i];
         index_sizes[i] = 0;
         if (x.done)
             continue;
@@ -676,6 +424,9 @@ try
         }
     }
 
+    // (the scans that get no seek points: the build call needs every scan's length, which charls_amd_decode_batch_device does
+    // not report; the launcher's clock is not reported, so it must not fail the call)
+    DecodeLauncher plain(stream, true);
     uint32_t params_from = UINT32_MAX;
     for (size_t scan_no = 0;; ++scan_no)
     {
@@ -685,7 +436,7 @@ try
         std::vector<uint8_t*> points_out;
         for (uint32_t i = 0; i < frame_count; ++i)
         {
-            Frame& x = s.fr[i];
+            BatchFrame& x = s.fr[i];
             if (x.done)
                 continue;
             try
@@ -726,7 +477,7 @@ try
             break;
         std::vector<ScanResult> emit_results, plain_results;
         run_emit(emit_descs, point_totals, points_out, lines, emit_results, stream);
-        run_ordinary(plain_descs, plain_results, stream);
+        plain.run(plain_descs, plain_results);
 
         // every scan's length and hash; then past it, to the next SOS or the end of the image
         std::vector<uint32_t> which;
@@ -734,7 +485,7 @@ try
         std::vector<uint8_t> last;
         std::vector<seek::HashJob> jobs;
         auto scan_done = [&](uint32_t i, const ScanResult& r) {
-            Frame& x = s.fr[i];
+            BatchFrame& x = s.fr[i];
             if (r.errc != kOk)
             {
                 x.errc = static_cast<charls_jpegls_errc>(r.errc);
@@ -748,12 +499,12 @@ try
                 return;
             }
             builds[i].index.scans[scan_no].segment_bytes = r.bytes;
-            jobs.push_back(seek::HashJob{static_cast<uint64_t>(i) * stream_pitch_bytes + x.cursor, r.bytes});
+            jobs.push_back(seek::HashJob{s.offset_of(i) + x.cursor, r.bytes});
             x.cursor += r.bytes;
             x.decoded_components += x.reader.scan_component_count();
             const bool end = x.decoded_components == x.reader.component_count();
             if (!end)
-                x.plane_offset += (stride_arg ? stride_arg : row_bytes_of(scan_spec_of(x.reader))) * x.reader.frame_info().height;
+                x.plane_offset += row_and_stride(x.reader, stride_arg).stride * x.reader.frame_info().height;
             which.push_back(i);
             bases.push_back(x.cursor);
             last.push_back(end ? 1 : 0);
@@ -768,7 +519,7 @@ try
         s.parse_behind_scans(s.fr, which, bases, last);
         for (size_t k = 0; k < which.size(); ++k)
         {
-            Frame& x = s.fr[which[k]];
+            BatchFrame& x = s.fr[which[k]];
             if (x.done || !last[k])
                 continue;
             x.done = true; // the end of the image has been read: the index is the frame's
@@ -797,8 +548,8 @@ namespace {
 
 // The frames of `s` that have an index with seek points for every scan: the walk over their scans (every SOS parsed on a copy
 // of the frame, `probe`).  A frame whose walk breaks off is left out (walks[k].ok = false).
-void walk_indexed_frames(Streams& s, const std::vector<SeekIndex>& parsed, std::vector<Frame>& probe, std::vector<Walk>& walks,
-                         const std::function<ScanDesc(uint32_t, const Frame&, size_t)>& scan_desc, bool want_points)
+void walk_indexed_frames(StreamWindows& s, const std::vector<SeekIndex>& parsed, std::vector<BatchFrame>& probe, std::vector<Walk>& walks,
+                         const std::function<ScanDesc(uint32_t, const BatchFrame&, size_t)>& scan_desc, bool want_points)
 {
     probe = s.fr;
     const uint32_t n = static_cast<uint32_t>(s.fr.size());
@@ -821,7 +572,7 @@ void walk_indexed_frames(Streams& s, const std::vector<SeekIndex>& parsed, std::
             const SeekIndex& index = parsed[w.frame];
             if (!w.ok || c >= index.scans.size() || w.descs.size() != c)
                 continue;
-            Frame& y = probe[w.frame];
+            BatchFrame& y = probe[w.frame];
             try
             {
                 const ScanSpec spec = scan_spec_of(y.reader);
@@ -879,17 +630,18 @@ try
     dev::require_device();
     auto stream = static_cast<hipStream_t>(hip_stream);
     auto* frames = static_cast<uint8_t*>(d_frames);
-    Streams s(frame_count, d_streams, stream_pitch_bytes, sizes, stream);
+    const std::vector<uint64_t> stream_at = slot_offsets(frame_count, stream_pitch_bytes, sizes);
+    StreamWindows s(frame_count, d_streams, stream_at.data(), sizes, stream);
     timings_begin();
-    s.read_headers();
+    s.read_headers(true);
     std::vector<SeekIndex> parsed;
     parse_indexes(s, indexes, index_pitch_bytes, index_sizes, parsed);
 
     // ---- the frames that can go through their index: every scan has seek points and is one the seek kernels take
-    std::vector<Frame> probe;
+    std::vector<BatchFrame> probe;
     std::vector<Walk> walks;
     walk_indexed_frames(s, parsed, probe, walks,
-                        [&](uint32_t i, const Frame& y, size_t) { return frame_scan_desc(s, i, y, frames, frame_pitch_bytes, stride_arg); }, true);
+                        [&](uint32_t i, const BatchFrame& y, size_t) { return frame_scan_desc(s, i, y, frames, frame_pitch_bytes, stride_arg); }, true);
     std::vector<uint8_t> ordinary(frame_count, 0);
     std::vector<uint8_t> with_points(frame_count, 0); // the frame's index has seek points: decoding it from the top is a fallback
     for (uint32_t i = 0; i < frame_count; ++i)
@@ -901,13 +653,13 @@ try
     std::vector<seek::HashJob> jobs;
     for (Walk& w : walks)
     {
-        const Frame& x = s.fr[w.frame];
+        const BatchFrame& x = s.fr[w.frame];
         const ScanSpec first = scan_spec_of(x.reader);
         for (size_t c = 0; w.ok && c < w.descs.size(); ++c)
             w.ok = !x.reader.height_from_dnl() && same_scan_parameters(w.specs[c], first) && seek_spec_eligible(w.specs[c]) &&
                    rows_aligned(w.descs[c]);
         for (size_t c = 0; w.ok && c < w.descs.size(); ++c)
-            jobs.push_back(seek::HashJob{static_cast<uint64_t>(w.frame) * stream_pitch_bytes + w.starts[c], parsed[w.frame].scans[c].segment_bytes});
+            jobs.push_back(seek::HashJob{s.offset_of(w.frame) + w.starts[c], parsed[w.frame].scans[c].segment_bytes});
     }
     {
         const std::vector<uint64_t> hashes = device_hashes(s, jobs);
@@ -998,7 +750,7 @@ try
     add_index_counters(from_points, 0, fallbacks, 0);
     for (uint32_t i = 0; i < frame_count; ++i)
         errcs[i] = s.fr[i].errc;
-    const charls_jpegls_errc rc = decode_ordinary(s, ordinary, frames, frame_pitch_bytes, stride_arg, params_out, params_from, errcs);
+    const charls_jpegls_errc rc = decode_ordinary(s, stream_pitch_bytes, ordinary, frames, frame_pitch_bytes, stride_arg, params_out, params_from, errcs);
     timings_end(); // (this call's seek and hash launches, not the ordinary launches of the frames that went that way)
     return rc;
 }
@@ -1026,9 +778,10 @@ try
     dev::require_device();
     auto stream = static_cast<hipStream_t>(hip_stream);
     auto* bands = static_cast<uint8_t*>(d_bands);
-    Streams s(frame_count, d_streams, stream_pitch_bytes, sizes, stream);
+    const std::vector<uint64_t> stream_at = slot_offsets(frame_count, stream_pitch_bytes, sizes);
+    StreamWindows s(frame_count, d_streams, stream_at.data(), sizes, stream);
     timings_begin();
-    s.read_headers();
+    s.read_headers(true);
     std::vector<SeekIndex> parsed;
     for (uint32_t i = 0; i < frame_count; ++i)
         if (index_sizes[i] != 0)
@@ -1039,7 +792,7 @@ try
     std::vector<size_t> strides(frame_count, 0);
     for (uint32_t i = 0; i < frame_count; ++i)
     {
-        Frame& x = s.fr[i];
+        BatchFrame& x = s.fr[i];
         if (x.done)
             continue;
         try
@@ -1060,11 +813,11 @@ try
             x.done = true;
         }
     }
-    auto band_desc = [&](uint32_t i, const Frame& y, size_t c) {
-        ScanDesc d = desc_from(scan_spec_of(y.reader));
+    auto band_desc = [&](uint32_t i, const BatchFrame& y, size_t c) {
+        ScanDesc d = desc_of(scan_spec_of(y.reader));
         d.pixels = bands + i * band_pitch_bytes + strides[i] * row_counts[i] * c;
         d.pixel_stride = strides[i];
-        d.stream = const_cast<uint8_t*>(s.slots) + i * s.stream_pitch + y.cursor;
+        d.stream = s.stream_ptr(i, y.cursor);
         d.stream_capacity = s.sizes[i] - y.cursor;
         d.line_scratch = nullptr;
         return d;
@@ -1072,7 +825,7 @@ try
 
     // ---- frames on the seek kernels: every scan is reached through the index (or the frame has one scan) and is one the
     // kernels take; the others are decoded whole on the ordinary path
-    std::vector<Frame> probe;
+    std::vector<BatchFrame> probe;
     std::vector<Walk> walks;
     walk_indexed_frames(s, parsed, probe, walks, band_desc, false);
     std::vector<uint8_t> whole(frame_count, 0), walked(frame_count, 0);
@@ -1080,7 +833,7 @@ try
         walked[w.frame] = 1;
     for (uint32_t i = 0; i < frame_count; ++i)
     {
-        const Frame& x = s.fr[i];
+        const BatchFrame& x = s.fr[i];
         if (x.done || walked[i])
             continue;
         if (scans_of_frame(x.reader) == 1)
@@ -1098,7 +851,7 @@ try
     std::vector<seek::HashJob> jobs;
     for (Walk& w : walks)
     {
-        const Frame& x = s.fr[w.frame];
+        const BatchFrame& x = s.fr[w.frame];
         const SeekIndex& index = parsed[w.frame];
         for (size_t c = 0; w.ok && c < w.descs.size(); ++c)
             w.ok = !x.reader.height_from_dnl() && seek_spec_eligible(w.specs[c]) && rows_aligned(w.descs[c]);
@@ -1106,7 +859,7 @@ try
         // hash is checked, not only those of scans with seek points)
         for (size_t c = 0; w.ok && c < index.scans.size(); ++c)
             if (index.scans[c].points != 0 || index.scans.size() > 1)
-                jobs.push_back(seek::HashJob{static_cast<uint64_t>(w.frame) * stream_pitch_bytes + w.starts[c], index.scans[c].segment_bytes});
+                jobs.push_back(seek::HashJob{s.offset_of(w.frame) + w.starts[c], index.scans[c].segment_bytes});
         if (!w.ok)
             whole[w.frame] = 1;
     }
@@ -1190,7 +943,7 @@ try
     add_index_counters(from_points, 0, 0, 0);
     for (size_t k = 0; k < scans.size(); ++k)
     {
-        Frame& x = s.fr[walks[walk_of[k]].frame];
+        BatchFrame& x = s.fr[walks[walk_of[k]].frame];
         for (const ScanResult& r : scans[k].results) // (the first error from the top of the band down, scan by scan)
             if (r.errc != kOk && x.errc == CHARLS_JPEGLS_ERRC_SUCCESS)
                 x.errc = static_cast<charls_jpegls_errc>(r.errc);
@@ -1204,13 +957,13 @@ try
     {
         if (!whole[i] || s.fr[i].done)
             continue;
-        const Frame& x = s.fr[i];
+        const BatchFrame& x = s.fr[i];
         const charls_frame_info& f = x.reader.frame_info();
-        const size_t row_bytes = row_bytes_of(scan_spec_of(x.reader));
+        const size_t row_bytes = row_and_stride(x.reader, 0).row;
         const size_t scans_n = scans_of_frame(x.reader);
         const size_t frame_bytes = checked_mul(checked_mul(row_bytes, f.height), scans_n);
         auto* area = static_cast<uint8_t*>(dev::seek_arena(kArenaFrame).ensure(frame_bytes));
-        const charls_jpegls_errc rc = charls_amd_decode_batch_device(1, s.slots + i * stream_pitch_bytes, stream_pitch_bytes, sizes + i, area,
+        const charls_jpegls_errc rc = charls_amd_decode_batch_device(1, s.slots + s.offset_of(i), stream_pitch_bytes, sizes + i, area,
                                                                      frame_bytes, 0, nullptr, errcs + i, hip_stream);
         if (rc != CHARLS_JPEGLS_ERRC_SUCCESS)
             return rc;

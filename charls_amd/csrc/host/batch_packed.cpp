@@ -18,39 +18,10 @@
 #include "../device/runtime.h"
 #include "batch_streams.h"
 #include "common.h"
+#include "event_timer.h"
 
 using namespace jls;
 using dev::hip_check;
-
-namespace {
-
-// GPU time of what is launched on `stream` between construction and stop_and_wait (hipEvents).
-struct LaunchTimer
-{
-    hipEvent_t a{}, b{};
-    hipStream_t s;
-    explicit LaunchTimer(hipStream_t stream) : s(stream)
-    {
-        hip_check(hipEventCreate(&a));
-        hip_check(hipEventCreate(&b));
-        hip_check(hipEventRecord(a, s));
-    }
-    ~LaunchTimer()
-    {
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-    }
-    double stop_and_wait()
-    {
-        float ms = 0;
-        hip_check(hipEventRecord(b, s));
-        hip_check(hipEventSynchronize(b));
-        hip_check(hipEventElapsedTime(&ms, a, b));
-        return ms;
-    }
-};
-
-} // namespace
 
 // charls_jpegls_encoder_get_estimated_destination_size for the frames of `p` (encoder_api.cpp; reference
 // src/charls_jpegls_encoder.cpp:103-114).  Parameters the encoder is going to refuse give 1: the call fails on them anyway.
@@ -113,10 +84,12 @@ try
     dev::DeviceBuffer d_jobs;
     d_jobs.ensure(sizeof(PackJob) * jobs.size());
     hip_check(hipMemcpyAsync(d_jobs.as<PackJob>(), jobs.data(), sizeof(PackJob) * jobs.size(), hipMemcpyHostToDevice, stream));
-    LaunchTimer timer(stream);
+    EventTimer timer(stream);
+    timer.start();
     dev::launch_pack_streams(static_cast<const uint8_t*>(d_streams), static_cast<uint8_t*>(d_packed), d_jobs.as<PackJob>(),
                              static_cast<uint32_t>(jobs.size()), longest, stream);
-    const double ms = timer.stop_and_wait(); // (the call returns after the stream work has completed)
+    timer.stop();
+    const double ms = timer.ms();          // (the call returns after the stream work has completed)
     dev::Timings& t = dev::last_timings();   // charls_amd_last_timings: [0] = [1] = the copy kernel
     t.values[0] = t.values[1] = ms;
     t.count = 2;

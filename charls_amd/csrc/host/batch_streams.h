@@ -1,5 +1,6 @@
 // batch_streams.h -- what the batch entry points share across translation units (batch_api.cpp, batch_packed.cpp,
-// batch_ragged.cpp).
+// batch_ragged.cpp, batch_budget.cpp).  The decoders' host plumbing -- window parser, ordinary launch -- is stream_windows.h
+// (batch_api.cpp, batch_index.cpp), the event-pair timer event_timer.h.
 #pragma once
 #include <cstdint>
 

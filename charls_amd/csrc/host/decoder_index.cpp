@@ -40,37 +40,26 @@ void store(uint8_t* p, T v) noexcept
     std::memcpy(p, &v, sizeof v);
 }
 
-ScanDesc desc_of(const ScanSpec& s) noexcept // (the fields ScanEngine::make_desc fills; no memory)
+int32_t planes_of(const ScanSpec& s) noexcept
 {
-    ScanDesc d{};
-    d.width = s.width;
-    d.height = s.height;
-    d.components = s.components;
-    d.interleave_mode = s.interleave_mode;
-    d.bits_per_sample = s.bits_per_sample;
-    d.near_lossless = s.near_lossless;
-    d.color_transformation = s.color_transformation;
-    d.t1 = s.pc.threshold1;
-    d.t2 = s.pc.threshold2;
-    d.t3 = s.pc.threshold3;
-    d.reset = static_cast<uint8_t>(s.pc.reset_value);
-    d.restart_interval = s.restart_interval;
-    return d;
+    return s.interleave_mode == 0 ? 1 : s.components;
 }
 
-bool spec_seek_eligible(const ScanSpec& s) noexcept
+} // namespace
+
+bool seek_spec_eligible(const ScanSpec& s) noexcept
 {
     return dev::seek_decode_eligible(desc_of(s)); // (device rows are packed: no odd row address for 16-bit samples)
 }
 
-bool same_parameters(const ScanSpec& a, const ScanSpec& b) noexcept
+bool same_scan_parameters(const ScanSpec& a, const ScanSpec& b) noexcept
 {
     return a.components == b.components && a.interleave_mode == b.interleave_mode && a.near_lossless == b.near_lossless &&
            a.color_transformation == b.color_transformation && a.restart_interval == b.restart_interval &&
            std::memcmp(&a.pc, &b.pc, sizeof a.pc) == 0;
 }
 
-ScanSpec current_spec(const StreamReader& r)
+ScanSpec scan_spec_of(const StreamReader& r)
 {
     const charls_frame_info& f = r.frame_info();
     return ScanSpec{f.width,
@@ -84,21 +73,37 @@ ScanSpec current_spec(const StreamReader& r)
                     r.parameters().restart_interval};
 }
 
-int32_t planes_of(const ScanSpec& s) noexcept
+size_t row_bytes_of(const ScanSpec& s) noexcept
 {
-    return s.interleave_mode == 0 ? 1 : s.components;
+    return static_cast<size_t>(planes_of(s)) * s.width * bytes_per_sample(s.bits_per_sample);
 }
-size_t point_bytes_of(const ScanSpec& s) noexcept
+size_t seek_point_bytes(const ScanSpec& s) noexcept
 {
     return seek::point_bytes(s.width, planes_of(s), s.bits_per_sample > 8);
 }
-size_t scans_of(const StreamReader& r) noexcept
+size_t scans_of_frame(const StreamReader& r) noexcept
 {
     return r.scan_interleave_mode() == 0 ? r.component_count() : 1;
 }
+
+charls_amd_codec_params params_of(const StreamReader& r)
+{
+    return charls_amd_codec_params{r.frame_info(), r.parameters().near_lossless, r.scan_interleave_mode(), r.parameters().transformation,
+                                   r.preset_coding_parameters(), 0, r.parameters().restart_interval};
+}
+
+RowStride row_and_stride(const StreamReader& r, size_t stride_arg) noexcept
+{
+    const charls_frame_info& f = r.frame_info();
+    const size_t row = (r.scan_interleave_mode() == 0 ? 1u : r.scan_component_count()) * static_cast<size_t>(f.width) * bytes_per_sample(f.bits_per_sample);
+    return RowStride{row, stride_arg != 0 ? stride_arg : row};
+}
+
+namespace {
+
 uint32_t expected_points(const StreamReader& r, const ScanSpec& first, uint32_t lines) noexcept
 {
-    return !r.height_from_dnl() && spec_seek_eligible(first) ? seek::points_per_scan(first.height, lines) : 0u;
+    return !r.height_from_dnl() && seek_spec_eligible(first) ? seek::points_per_scan(first.height, lines) : 0u;
 }
 
 // One seek point against the ranges a true decoder state keeps (A.12/A.13 and the kernel's packed forms): so that a forged
@@ -170,44 +175,23 @@ void add_index_counters(uint64_t scans_from_points, uint64_t intervals, uint64_t
     g_launches.fetch_add(launches);
 }
 
-ScanSpec scan_spec_of(const StreamReader& reader)
-{
-    return current_spec(reader);
-}
-size_t scans_of_frame(const StreamReader& reader) noexcept
-{
-    return scans_of(reader);
-}
-bool same_scan_parameters(const ScanSpec& a, const ScanSpec& b) noexcept
-{
-    return same_parameters(a, b);
-}
-bool seek_spec_eligible(const ScanSpec& spec) noexcept
-{
-    return spec_seek_eligible(spec);
-}
-size_t seek_point_bytes(const ScanSpec& spec) noexcept
-{
-    return point_bytes_of(spec);
-}
-
 size_t index_size_bound(const ScanSpec& first, size_t scans, bool height_from_dnl, uint32_t lines)
 {
     check_argument(lines > 0);
-    const uint32_t points = !height_from_dnl && spec_seek_eligible(first) ? seek::points_per_scan(first.height, lines) : 0u;
-    return kIndexHeaderBytes + scans * (kIndexScanBytes + points * point_bytes_of(first));
+    const uint32_t points = !height_from_dnl && seek_spec_eligible(first) ? seek::points_per_scan(first.height, lines) : 0u;
+    return kIndexHeaderBytes + scans * (kIndexScanBytes + points * seek_point_bytes(first));
 }
 
 size_t index_size_bound(const StreamReader& reader, uint32_t lines)
 {
-    return index_size_bound(current_spec(reader), scans_of(reader), reader.height_from_dnl(), lines);
+    return index_size_bound(scan_spec_of(reader), scans_of_frame(reader), reader.height_from_dnl(), lines);
 }
 
 SeekIndex parse_index(const StreamReader& reader, const uint8_t* data, size_t bytes)
 {
     check_argument(data != nullptr && bytes >= kIndexHeaderBytes);
     check_argument(std::memcmp(data, kMagic, sizeof kMagic) == 0 && load<uint32_t>(data + 8) == kIndexVersion);
-    const ScanSpec first = current_spec(reader);
+    const ScanSpec first = scan_spec_of(reader);
     const charls_frame_info& f = reader.frame_info();
     SeekIndex index;
     index.lines = load<uint32_t>(data + 12);
@@ -218,10 +202,10 @@ SeekIndex parse_index(const StreamReader& reader, const uint8_t* data, size_t by
                    load<int32_t>(data + 32) == first.interleave_mode && load<int32_t>(data + 36) == first.near_lossless &&
                    load<int32_t>(data + 40) == first.pc.threshold1 && load<int32_t>(data + 44) == first.pc.threshold2 &&
                    load<int32_t>(data + 48) == first.pc.threshold3 && load<int32_t>(data + 52) == first.pc.reset_value &&
-                   load<int32_t>(data + 56) == first.color_transformation && scans == scans_of(reader) &&
-                   load<uint32_t>(data + 64) == point_bytes_of(first) && load<uint32_t>(data + 68) == 0);
+                   load<int32_t>(data + 56) == first.color_transformation && scans == scans_of_frame(reader) &&
+                   load<uint32_t>(data + 64) == seek_point_bytes(first) && load<uint32_t>(data + 68) == 0);
     const uint32_t expected = expected_points(reader, first, index.lines);
-    const size_t point_bytes = point_bytes_of(first);
+    const size_t point_bytes = seek_point_bytes(first);
     check_argument(bytes >= kIndexHeaderBytes + scans * kIndexScanBytes);
     size_t at = kIndexHeaderBytes + scans * kIndexScanBytes;
     index.scans.resize(scans);
@@ -248,7 +232,7 @@ SeekIndex parse_index(const StreamReader& reader, const uint8_t* data, size_t by
 
 size_t write_index(const StreamReader& reader, const SeekIndex& index, uint8_t* out, size_t capacity)
 {
-    const ScanSpec first = current_spec(reader);
+    const ScanSpec first = scan_spec_of(reader);
     const charls_frame_info& f = reader.frame_info();
     size_t total = kIndexHeaderBytes + index.scans.size() * kIndexScanBytes;
     for (const IndexScan& s : index.scans)
@@ -270,7 +254,7 @@ size_t write_index(const StreamReader& reader, const SeekIndex& index, uint8_t* 
     store<int32_t>(out + 52, first.pc.reset_value);
     store<int32_t>(out + 56, first.color_transformation);
     store<uint32_t>(out + 60, static_cast<uint32_t>(index.scans.size()));
-    store<uint32_t>(out + 64, static_cast<uint32_t>(point_bytes_of(first)));
+    store<uint32_t>(out + 64, static_cast<uint32_t>(seek_point_bytes(first)));
     size_t at = kIndexHeaderBytes + index.scans.size() * kIndexScanBytes;
     for (size_t c = 0; c < index.scans.size(); ++c)
     {
@@ -284,7 +268,7 @@ size_t write_index(const StreamReader& reader, const SeekIndex& index, uint8_t* 
             std::memcpy(out + at, s.data.data(), s.data.size());
         // (the kernel writes a point's samples, not the bytes that pad its line to 8: they are zero in the file, whatever the
         // device buffer held, so that one stream has one index)
-        const size_t point_bytes = point_bytes_of(first);
+        const size_t point_bytes = seek_point_bytes(first);
         const size_t raw = static_cast<size_t>(planes_of(first)) * (static_cast<size_t>(first.width) + 2) * (first.bits_per_sample > 8 ? 2 : 1);
         const size_t pad = seek::line_bytes(first.width, planes_of(first), first.bits_per_sample > 8) - raw;
         for (size_t i = 0; pad != 0 && i < s.points && (i + 1) * point_bytes <= s.data.size(); ++i)
@@ -298,14 +282,14 @@ size_t decode_scan_indexed(ScanEngine& engine, const ScanSpec& spec, const ScanS
                            size_t segment_left, uint8_t* destination, size_t stride, size_t scan_no, IndexMode mode, SeekIndex& index,
                            bool seek_allowed)
 {
-    const bool eligible = seek_allowed && same_parameters(spec, first) && engine.seek_eligible(spec);
+    const bool eligible = seek_allowed && same_scan_parameters(spec, first) && engine.seek_eligible(spec);
     if (mode == IndexMode::build)
     {
         if (index.scans.size() <= scan_no)
             index.scans.resize(scan_no + 1);
         IndexScan& s = index.scans[scan_no];
         s.points = eligible ? seek::points_per_scan(spec.height, index.lines) : 0u;
-        s.data.assign(static_cast<size_t>(s.points) * point_bytes_of(spec), 0);
+        s.data.assign(static_cast<size_t>(s.points) * seek_point_bytes(spec), 0);
         const size_t used = s.points != 0 ? engine.decode_scan_emit(spec, stream_offset, destination, stride, index.lines, s.data.data())
                                           : engine.decode_scan(spec, stream_offset, destination, stride);
         s.segment_bytes = used;
@@ -329,9 +313,9 @@ void decode_rows(const StreamReader& reader, ScanEngine& engine, const SeekIndex
 {
     const charls_frame_info& f = reader.frame_info();
     check_argument(row_count > 0 && first_row < f.height && row_count <= f.height - first_row);
-    const ScanSpec first = current_spec(reader);
-    const size_t scans = scans_of(reader);
-    const size_t row_bytes = static_cast<size_t>(planes_of(first)) * f.width * bytes_per_sample(f.bits_per_sample);
+    const ScanSpec first = scan_spec_of(reader);
+    const size_t scans = scans_of_frame(reader);
+    const size_t row_bytes = row_bytes_of(first);
     const size_t stride = stride_arg == 0 ? row_bytes : stride_arg;
     check_argument(stride >= row_bytes, CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_STRIDE);
     const size_t needed = checked_mul(checked_mul(stride, row_count), scans) - (stride - row_bytes);
@@ -344,7 +328,7 @@ void decode_rows(const StreamReader& reader, ScanEngine& engine, const SeekIndex
     engine.upload_stream(base, reader.remaining(), frame_hint(f.width, f.height, f.bits_per_sample));
     for (size_t c = 0; c < scans; ++c)
     {
-        const ScanSpec spec = current_spec(probe);
+        const ScanSpec spec = scan_spec_of(probe);
         const size_t offset = static_cast<size_t>(probe.position() - base);
         uint8_t* dst = destination + stride * row_count * c;
         const uint8_t* points = nullptr;
@@ -352,7 +336,7 @@ void decode_rows(const StreamReader& reader, ScanEngine& engine, const SeekIndex
         { // a band cannot be checked by chaining: the index must belong to this very segment
             const IndexScan& s = index->scans[c];
             check_argument(s.segment_bytes <= probe.remaining() && segment_hash(probe.position(), s.segment_bytes) == s.hash);
-            if (same_parameters(spec, first))
+            if (same_scan_parameters(spec, first))
                 points = s.data.data();
         }
         if (!reader.height_from_dnl() && engine.seek_eligible(spec))
@@ -389,18 +373,17 @@ void decode_rows(const StreamReader& reader, ScanEngine& engine, const SeekIndex
 
 bool ScanEngine::seek_eligible(const ScanSpec& spec) const
 {
-    return spec_seek_eligible(spec);
+    return seek_spec_eligible(spec);
 }
 
 size_t ScanEngine::decode_scan_emit(const ScanSpec& spec, size_t stream_offset, uint8_t* destination, size_t stride, uint32_t lines,
                                     uint8_t* points)
 {
     ensure_stream();
-    const size_t planes = static_cast<size_t>(planes_of(spec));
-    const size_t row_bytes = planes * spec.width * bytes_per_sample(spec.bits_per_sample);
-    const size_t point_bytes = point_bytes_of(spec);
+    const size_t row_bytes = row_bytes_of(spec);
+    const size_t point_bytes = seek_point_bytes(spec);
     const size_t point_total = static_cast<size_t>(seek::points_per_scan(spec.height, lines)) * point_bytes;
-    ScanDesc d = make_desc(spec);
+    ScanDesc d = desc_of(spec);
     d.pixels = static_cast<uint8_t*>(r_->pixels.ensure(row_bytes * spec.height));
     d.pixel_stride = row_bytes;
     d.stream = r_->bits.as<uint8_t>() + stream_offset;
@@ -438,12 +421,11 @@ bool ScanEngine::decode_scan_resumed(const ScanSpec& spec, size_t stream_offset,
                                      const uint8_t* points, size_t& used)
 {
     ensure_stream();
-    const size_t planes = static_cast<size_t>(planes_of(spec));
-    const size_t row_bytes = planes * spec.width * bytes_per_sample(spec.bits_per_sample);
-    const size_t point_bytes = point_bytes_of(spec);
+    const size_t row_bytes = row_bytes_of(spec);
+    const size_t point_bytes = seek_point_bytes(spec);
     const uint32_t count = seek::points_per_scan(spec.height, lines);
     const uint32_t intervals = count + 1;
-    ScanDesc d = make_desc(spec);
+    ScanDesc d = desc_of(spec);
     d.pixels = static_cast<uint8_t*>(r_->pixels.ensure(row_bytes * spec.height));
     d.pixel_stride = row_bytes;
     d.stream = r_->bits.as<uint8_t>() + stream_offset;
@@ -491,9 +473,8 @@ void ScanEngine::decode_scan_band(const ScanSpec& spec, size_t stream_offset, ui
                                   uint32_t rows, uint32_t lines, const uint8_t* points)
 {
     ensure_stream();
-    const size_t planes = static_cast<size_t>(planes_of(spec));
-    const size_t row_bytes = planes * spec.width * bytes_per_sample(spec.bits_per_sample);
-    const size_t point_bytes = point_bytes_of(spec);
+    const size_t row_bytes = row_bytes_of(spec);
+    const size_t point_bytes = seek_point_bytes(spec);
     const uint32_t count = points != nullptr ? seek::points_per_scan(spec.height, lines) : 0u;
     const uint32_t end = first_row + rows;
     // with seek points, every interval the band touches is a wavefront of its own (point i starts row i * lines); without,
@@ -513,7 +494,7 @@ void ScanEngine::decode_scan_band(const ScanSpec& spec, size_t stream_offset, ui
         work.push_back(w);
     }
     const uint32_t n = static_cast<uint32_t>(work.size());
-    ScanDesc d = make_desc(spec);
+    ScanDesc d = desc_of(spec);
     d.pixels = static_cast<uint8_t*>(r_->pixels.ensure(row_bytes * rows));
     d.pixel_stride = row_bytes;
     d.stream = r_->bits.as<uint8_t>() + stream_offset;

@@ -431,24 +431,6 @@ void ScanEngine::end_call() noexcept
     announced_lane_ = -1;
 }
 
-ScanDesc ScanEngine::make_desc(const ScanSpec& s) const
-{
-    ScanDesc d{};
-    d.width = s.width;
-    d.height = s.height;
-    d.components = s.components;
-    d.interleave_mode = s.interleave_mode;
-    d.bits_per_sample = s.bits_per_sample;
-    d.near_lossless = s.near_lossless;
-    d.color_transformation = s.color_transformation;
-    d.t1 = s.pc.threshold1;
-    d.t2 = s.pc.threshold2;
-    d.t3 = s.pc.threshold3;
-    d.reset = static_cast<uint8_t>(s.pc.reset_value); // reference src/scan_codec.hpp:142
-    d.restart_interval = s.restart_interval;
-    return d;
-}
-
 ScanResult ScanEngine::run(const ScanDesc& desc, bool decode)
 {
     ScanResult r;
@@ -572,7 +554,7 @@ void ScanEngine::encode_planes(const ScanSpec& spec, uint32_t count, size_t plan
     auto* bits = static_cast<uint8_t*>(r_->bits.ensure(plane_capacity_ * count));
     const size_t scratch_samples = dev::line_scratch_samples(spec.width, spec.interleave_mode, spec.components);
     auto* scratch = static_cast<uint16_t*>(r_->scratch.ensure(scratch_samples * sizeof(uint16_t) * count));
-    std::vector<ScanDesc> descs(count, make_desc(spec));
+    std::vector<ScanDesc> descs(count, desc_of(spec));
     for (uint32_t c = 0; c < count; ++c)
     {
         descs[c].pixels = r_->pixels.as<uint8_t>() + plane_bytes * c;
@@ -597,7 +579,7 @@ void ScanEngine::decode_planes(const ScanSpec& spec, const size_t* stream_offset
     auto* pixels = static_cast<uint8_t*>(r_->pixels.ensure(plane * count));
     const size_t scratch_samples = dev::line_scratch_samples(spec.width, spec.interleave_mode, spec.components);
     auto* scratch = static_cast<uint16_t*>(r_->scratch.ensure(scratch_samples * sizeof(uint16_t) * count));
-    std::vector<ScanDesc> descs(count, make_desc(spec));
+    std::vector<ScanDesc> descs(count, desc_of(spec));
     for (uint32_t c = 0; c < count; ++c)
     {
         descs[c].pixels = pixels + plane * c;
@@ -657,7 +639,7 @@ size_t ScanEngine::encode_scan(const ScanSpec& spec, size_t pixel_offset, size_t
     // Never allocate more than the scan can possibly produce; a larger destination behaves identically.
     const size_t bound = dev::worst_case_scan_bytes(spec.width, spec.height, spec.components, spec.bits_per_sample);
     const size_t capacity = std::min(destination_size, bound);
-    ScanDesc d = make_desc(spec);
+    ScanDesc d = desc_of(spec);
     d.pixels = r_->pixels.as<uint8_t>() + pixel_offset;
     d.pixel_stride = stride;
     d.stream = static_cast<uint8_t*>(r_->bits.ensure(capacity));
@@ -688,7 +670,7 @@ size_t ScanEngine::decode_scan(const ScanSpec& spec, size_t stream_offset, uint8
     ensure_stream();
     const size_t planes = spec.interleave_mode == 0 ? 1 : static_cast<size_t>(spec.components);
     const size_t row_bytes = planes * spec.width * bytes_per_sample(spec.bits_per_sample);
-    ScanDesc d = make_desc(spec);
+    ScanDesc d = desc_of(spec);
     d.pixels = static_cast<uint8_t*>(r_->pixels.ensure(row_bytes * spec.height)); // device rows are packed
     d.pixel_stride = row_bytes;
     d.stream = r_->bits.as<uint8_t>() + stream_offset;

@@ -23,6 +23,25 @@ struct ScanSpec
     uint32_t restart_interval;
 };
 
+// The scan's geometry and coding parameters as the kernels take them; the pointers, strides and capacities are the caller's.
+inline ScanDesc desc_of(const ScanSpec& s) noexcept
+{
+    ScanDesc d{};
+    d.width = s.width;
+    d.height = s.height;
+    d.components = s.components;
+    d.interleave_mode = s.interleave_mode;
+    d.bits_per_sample = s.bits_per_sample;
+    d.near_lossless = s.near_lossless;
+    d.color_transformation = s.color_transformation;
+    d.t1 = s.pc.threshold1;
+    d.t2 = s.pc.threshold2;
+    d.t3 = s.pc.threshold3;
+    d.reset = static_cast<uint8_t>(s.pc.reset_value); // reference src/scan_codec.hpp:142
+    d.restart_interval = s.restart_interval;
+    return d;
+}
+
 // What a handle needs on the device: a stream, the device copies of pixels and coded bytes, descriptors, a pinned
 // staging area.  The reference's callers create an encoder or decoder per image (cli/benchmark.cpp does, inside its
 // clock); creating and destroying these per handle cost more than coding a 4096 x 4096 frame (hipStreamCreate, five
@@ -130,7 +149,6 @@ public:
 
 private:
     void ensure_stream();
-    ScanDesc make_desc(const ScanSpec& spec) const;
     ScanResult run(const ScanDesc& desc, bool decode);
     void run_many(const ScanDesc* descs, uint32_t count, bool decode, ScanResult* results);
     void launch(const ScanDesc* descs, uint32_t n, bool decode, ScanResult* results, hipStream_t stream);

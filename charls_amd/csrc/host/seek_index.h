@@ -84,6 +84,17 @@ bool same_scan_parameters(const ScanSpec& a, const ScanSpec& b) noexcept;
 // The kernels' conditions on the parameters alone (where the rows lie is the caller's to check).
 bool seek_spec_eligible(const ScanSpec& spec) noexcept;
 size_t seek_point_bytes(const ScanSpec& spec) noexcept;
+size_t row_bytes_of(const ScanSpec& spec) noexcept; // of a row of the scan as the caller holds it: all its components where interleaved
+// What params_out says about a frame whose reader stands behind the header of its first scan.
+charls_amd_codec_params params_of(const StreamReader& reader);
+// The bytes of a row of the scan whose header `reader` has read, and the bytes from row to row for a caller's stride
+// argument (0: the row's; whether a stride covers the row is the caller's to check).  Needs no valid preset parameters,
+// which scan_spec_of raises for: the batch decoders check strides and capacities before them, as part 1 does.
+struct RowStride
+{
+    size_t row, stride;
+};
+RowStride row_and_stride(const StreamReader& reader, size_t stride_arg) noexcept;
 // index_size_bound for a frame of `scans` scans with this first scan.
 size_t index_size_bound(const ScanSpec& first, size_t scans, bool height_from_dnl, uint32_t lines);
 void add_index_counters(uint64_t scans_from_points, uint64_t intervals, uint64_t fallbacks, uint64_t launches) noexcept;
