@@ -110,6 +110,12 @@ def _bind(lib):
     l.charls_amd_encode_batch_device_budget.restype = C.c_int32
     l.charls_amd_measure_counters.argtypes = [u64p, C.c_int32]
     l.charls_amd_measure_counters.restype = C.c_int32
+    l.charls_amd_decode_batch_device_salvage.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.POINTER(FrameDest), C.c_uint32,
+                                                         C.POINTER(CodecParams), C.POINTER(capi.SalvageReport), C.c_void_p, C.c_size_t,
+                                                         i32p, C.c_void_p]
+    l.charls_amd_decode_batch_device_salvage.restype = C.c_int32
+    l.charls_amd_salvage_counters.argtypes = [u64p, C.c_int32]
+    l.charls_amd_salvage_counters.restype = C.c_int32
     l._batch_bound = True
     return l
 
@@ -456,6 +462,22 @@ def probe_packed(packed, offsets, sizes, *, lib=None):
     return params, frame_bytes, errcs
 
 
+def _frame_dests(outs, strides, capacities):
+    dests = (FrameDest * max(len(outs), 1))()
+    for f, t in enumerate(outs):
+        assert t.is_cuda
+        assert strides is not None or t.is_contiguous() or t.dim() == 2, "a 3-D view: say its row stride (planar or interleaved?)"
+        stride = strides[f] if strides is not None else _row_stride(t, False)
+        if capacities is not None:
+            capacity = int(capacities[f])
+        elif t.is_contiguous():
+            capacity = t.numel() * t.element_size()
+        else:  # the view's extent: to the end of its last row
+            capacity = (sum((n - 1) * s for n, s in zip(t.shape, t.stride())) + 1) * t.element_size()
+        dests[f] = FrameDest(t.data_ptr(), capacity, int(stride), 0)
+    return dests
+
+
 def decode_batch_ragged(packed, offsets, sizes, outs, *, strides=None, capacities=None, lib=None):
     """charls_amd_decode_batch_device_ragged: frame f of the packed streams into outs[f], a device tensor of its own (any
     allocation, any shape of enough bytes; a view with padded rows states them through its strides).  strides / capacities:
@@ -468,18 +490,7 @@ def decode_batch_ragged(packed, offsets, sizes, outs, *, strides=None, capacitie
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     count = len(sizes)
     assert len(offsets) >= count and len(outs) == count
-    dests = (FrameDest * max(count, 1))()
-    for f, t in enumerate(outs):
-        assert t.is_cuda
-        assert strides is not None or t.is_contiguous() or t.dim() == 2, "a 3-D view: say its row stride (planar or interleaved?)"
-        stride = strides[f] if strides is not None else _row_stride(t, False)
-        if capacities is not None:
-            capacity = int(capacities[f])
-        elif t.is_contiguous():
-            capacity = t.numel() * t.element_size()
-        else:  # the view's extent: to the end of its last row
-            capacity = (sum((n - 1) * s for n, s in zip(t.shape, t.stride())) + 1) * t.element_size()
-        dests[f] = FrameDest(t.data_ptr(), capacity, int(stride), 0)
+    dests = _frame_dests(outs, strides, capacities)
     params = (CodecParams * max(count, 1))()
     errcs = np.zeros(count, dtype=np.int32)
     stream = torch.cuda.current_stream(packed.device).cuda_stream
@@ -489,6 +500,52 @@ def decode_batch_ragged(packed, offsets, sizes, outs, *, strides=None, capacitie
     if rc != 0:
         raise capi.JpegLSError(rc, "charls_amd_decode_batch_device_ragged")
     return params, errcs, last_timings(lib)
+
+
+@dataclass
+class SalvagedBatch:
+    params: object       # ctypes array, one CodecParams per frame
+    errcs: np.ndarray    # int32: what decode_batch_ragged reports
+    reports: object      # ctypes array, one capi.SalvageReport per frame (state 1: the destination is usable)
+    status: np.ndarray   # (frames, status_pitch) uint8, one byte per (scan, interval) of a salvaged frame; None when not asked for
+    gpu_ms: tuple        # last_timings: round 1's (total, dominant kernel); with a round 2, what that round took (host clock)
+
+
+def decode_batch_salvage(packed, offsets, sizes, outs, fill_value=0, *, strides=None, capacities=None, status_pitch=0, lib=None) -> SalvagedBatch:
+    """charls_amd_decode_batch_device_salvage: decode_batch_ragged, and for the frames it fails on that have restart
+    intervals the intact intervals, with fill_value in the rows of the lost ones (reports[f].state == 1).  status_pitch > 0:
+    also the status byte of every (scan, interval): 0 kept, 1 unclaimed, 2 not decodable to its exact length, 3 scan not reached."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert packed.is_cuda and packed.is_contiguous()
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    count = len(sizes)
+    assert len(offsets) >= count and len(outs) == count
+    dests = _frame_dests(outs, strides, capacities)
+    params = (CodecParams * max(count, 1))()
+    reports = (capi.SalvageReport * max(count, 1))()
+    errcs = np.zeros(count, dtype=np.int32)
+    status = np.full((max(count, 1), status_pitch), 0xFF, dtype=np.uint8) if status_pitch else None
+    stream = torch.cuda.current_stream(packed.device).cuda_stream
+    rc = l.charls_amd_decode_batch_device_salvage(count, packed.data_ptr(), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                  sizes.ctypes.data_as(C.POINTER(C.c_uint64)), dests, int(fill_value), params, reports,
+                                                  status.ctypes.data if status is not None else None, status_pitch,
+                                                  errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_decode_batch_device_salvage")
+    return SalvagedBatch(params, errcs, reports, status, last_timings(lib))
+
+
+def salvage_counters(lib=None):
+    """charls_amd_salvage_counters: (frames salvaged, intervals kept, intervals lost, launches of the salvage kernels),
+    process-wide since the library was loaded."""
+    l = _bind(lib or capi.load_product())
+    out = (C.c_uint64 * 4)()
+    n = l.charls_amd_salvage_counters(out, 4)
+    assert n == 4
+    return tuple(int(out[i]) for i in range(4))
 
 
 def encode_batch_ragged(frames, params, packed, *, alignment=1, strides=None, max_stream_bytes=None, capacity=None, lib=None) -> PackedBatch:

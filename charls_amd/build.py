@@ -41,6 +41,7 @@ SOURCES = [
     "host/batch_packed.cpp",
     "host/batch_ragged.cpp",
     "host/batch_budget.cpp",
+    "host/batch_salvage.cpp",
     "host/multi_device.cpp",
 ]
 

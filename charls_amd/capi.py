@@ -48,6 +48,14 @@ class SpiffHeader(C.Structure):  # include/charls/public_types.h:934-980 (40 byt
                 ("vertical_resolution", C.c_uint32), ("horizontal_resolution", C.c_uint32)]
 
 
+class SalvageReport(C.Structure):  # charls_amd_salvage_report (include/charls_amd.h part 2g; product library only)
+    _fields_ = [("state", C.c_uint32), ("intervals", C.c_uint32), ("intervals_lost", C.c_uint32), ("rows_lost", C.c_uint32),
+                ("first_lost_row", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def astuple(self):
+        return (self.state, self.intervals, self.intervals_lost, self.rows_lost, self.first_lost_row, self.reserved)
+
+
 class MappingTableInfo(C.Structure):  # include/charls/public_types.h:1024-1034 (12 bytes)
     _fields_ = [("table_id", C.c_int32), ("entry_size", C.c_int32), ("data_size", C.c_uint32)]
 
@@ -347,6 +355,30 @@ class CharLSLibrary:
             self._check(L.charls_jpegls_decoder_decode_to_buffer(dec, out.ctypes.data, out.nbytes, stride), "decode_to_buffer")
             del keep
             return hdr, out
+        finally:
+            L.charls_jpegls_decoder_destroy(dec)
+
+    def decode_salvage(self, data, fill_value=0, stride=0, status_capacity=None):
+        """charls_amd_jpegls_decoder_decode_to_buffer_salvage (product library only): (Header, raw destination bytes,
+        SalvageReport, status bytes, errc).  errc is what decode_to_buffer returns; with report.state == 1 the destination holds
+        the intact restart intervals and fill_value elsewhere.  status_capacity: room for the status bytes (default: enough)."""
+        L = self.lib
+        fn = L.charls_amd_jpegls_decoder_decode_to_buffer_salvage
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(SalvageReport), C.c_void_p, C.c_size_t]
+        fn.restype = C.c_int32
+        dec, keep = self._open(data)
+        try:
+            hdr = self._header(dec)
+            sz = C.c_size_t()
+            self._check(L.charls_jpegls_decoder_get_destination_size(dec, stride, C.byref(sz)), "get_dest_size")
+            out = np.zeros(sz.value, dtype=np.uint8)
+            if status_capacity is None:
+                status_capacity = hdr.component_count * hdr.height
+            status = np.full(max(status_capacity, 1), 0xFF, dtype=np.uint8)
+            report = SalvageReport()
+            rc = fn(dec, out.ctypes.data, out.nbytes, stride, fill_value, C.byref(report), status.ctypes.data, status_capacity)
+            del keep
+            return hdr, out, report, status[:status_capacity], rc
         finally:
             L.charls_jpegls_decoder_destroy(dec)
 

@@ -110,6 +110,24 @@ uint64_t decode_launch_key(const ScanDesc& d) noexcept;
 void launch_decode(const ScanDesc& proto, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
                    hipStream_t stream);
 
+// Salvage decode (salvage_intervals.hip; charls_amd.h part 2g): what launch_decode cannot decode whole, by restart intervals.
+// A scan qualifies when its intervals can be decoded as scans of their own; scans with equal keys share a launch (they have
+// the same geometry, height and restart interval).
+bool salvage_candidate(const ScanDesc& d) noexcept;
+uint64_t salvage_launch_key(const ScanDesc& d) noexcept;
+struct SalvageOutputs
+{
+    uint32_t fill_value;    // the sample value for the rows of lost intervals
+    uint8_t* status;        // HOST, count * intervals: one byte per (scan, interval), salvage::kKept ..
+    uint64_t* segment_ends; // HOST, count: where scan i's entropy-coded segment ends, from its first byte (its capacity: no marker)
+};
+// Decodes the intervals of the `count` scans at d_descs as far as their markers can be trusted and fills the rows of the rest;
+// a scan with stream_capacity 0 was not reached: all its rows are filled.  Synchronises: the outputs are there on return.
+// Its buffers are work areas of the calling thread.
+void launch_decode_salvage(const ScanDesc& proto, const ScanDesc* d_descs, uint32_t count, const SalvageOutputs& outputs,
+                           hipStream_t stream);
+uint64_t salvage_kernel_launches() noexcept; // launches of the three salvage kernels since the library was loaded
+
 // Encoder dispatch.  All `count` scans share the geometry / coding mode of `proto` (HOST copy of one of them; its
 // stream_capacity is an upper bound of every scan's capacity).  Lossless single-component scans go through the
 // parallel pipeline (tile_pipeline.hip) unless the engine is forced to serial; everything else, and the rare scan

@@ -20,6 +20,7 @@
 #include "scan_group_decode.hip"
 #include "group_launch.h"
 #include "restart_intervals.hip"
+#include "salvage_intervals.hip"
 #include "seek_decode.h"
 
 namespace jls::dev {
@@ -255,6 +256,7 @@ Timings& last_timings() noexcept
 
 namespace {
 std::atomic<uint64_t> g_speculation[tile_counter_count]{};
+std::atomic<uint64_t> g_salvage_launches{0}; // launches of the kernels of salvage_intervals.hip
 std::atomic<uint64_t> g_exact_retry_scans{0}; // scans a speed-path decoder handed to the exact decoder (it did not end cleanly there)
 std::atomic<uint64_t> g_serial_fallback_scans{0}; // scans the tile pipeline was eligible for that ran on the one-wavefront kernel: no work area
 void note_pipeline_fallback(uint32_t scans) noexcept
@@ -269,6 +271,10 @@ uint64_t pipeline_fallback_scans() noexcept
 uint64_t exact_retry_scans() noexcept
 {
     return g_exact_retry_scans.load();
+}
+uint64_t salvage_kernel_launches() noexcept
+{
+    return g_salvage_launches.load();
 }
 void speculation_counters(uint64_t out[tile_counter_count]) noexcept
 {
@@ -312,11 +318,17 @@ bool wave_decode_eligible(const ScanDesc& d)
     return true;
 }
 
-// Scans whose restart intervals are decoded as scans of their own (restart_intervals.hip).
-bool interval_decode_candidate(const ScanDesc& d)
+// Scans whose restart intervals can be decoded as scans of their own (restart_intervals.hip, salvage_intervals.hip).
+bool intervals_decodable(const ScanDesc& d)
 {
     return d.restart_interval != 0 && d.restart_interval < d.height && d.height <= 65535 && d.restart_interval <= 65535 &&
-           wave_decode_eligible(d) && knobs::get_or(knobs::kSequentialIntervals, 0) == 0;
+           wave_decode_eligible(d);
+}
+
+// ... and are, by the ordinary decode.
+bool interval_decode_candidate(const ScanDesc& d)
+{
+    return intervals_decodable(d) && knobs::get_or(knobs::kSequentialIntervals, 0) == 0;
 }
 
 size_t fast_decode_lds(const ScanDesc& d)
@@ -516,6 +528,10 @@ bool seek_decode_eligible(const ScanDesc& d) noexcept
     return d.restart_interval == 0 && wave_decode_eligible(d);
 }
 
+namespace {
+uint64_t interval_launch_key(const ScanDesc& d, uint64_t base) noexcept;
+}
+
 uint64_t decode_launch_key(const ScanDesc& d) noexcept
 {
     // width | components | interleave | near-lossless | eligible | wide | exact-eligible : scans with equal keys can share a
@@ -527,11 +543,30 @@ uint64_t decode_launch_key(const ScanDesc& d) noexcept
                           (d.bits_per_sample > 8 ? 2u : 0u) | (wave_decode_eligible(d) ? 1u : 0u);
     if (!interval_decode_candidate(d))
         return base;
+    return interval_launch_key(d, base);
+}
+
+bool salvage_candidate(const ScanDesc& d) noexcept
+{
+    return intervals_decodable(d);
+}
+
+uint64_t salvage_launch_key(const ScanDesc& d) noexcept
+{
+    ScanDesc plain = d;
+    plain.restart_interval = 0; // (the key of the interval scans' own launch, whatever SEQUENTIAL_INTERVALS says)
+    return interval_launch_key(d, decode_launch_key(plain));
+}
+
+namespace {
+uint64_t interval_launch_key(const ScanDesc& d, uint64_t base) noexcept
+{
     // interval-parallel decode also needs equal height and restart interval (both < 2^16 here, as is the width)
     return (uint64_t{1} << 63) | (static_cast<uint64_t>(d.restart_interval) << 47) | (static_cast<uint64_t>(d.height) << 31) |
            (static_cast<uint64_t>(d.width & 0xFFFF) << 15) | (static_cast<uint64_t>(d.components & 7) << 12) |
            (static_cast<uint64_t>(d.interleave_mode & 3) << 10) | (base & 15u);
 }
+} // namespace
 
 namespace {
 // Side streams of the pipeline (per thread and device): the stuffing stage of a pass runs on one of them under the next pass's
@@ -575,9 +610,10 @@ struct PipelineLanes
 // set per device that is shared by all calling threads (SharedAreasScope), so that a pool of 256 threads does not end up with
 // 256 arenas.
 constexpr int kIntervalArenas = 8;
+constexpr int kSalvageArenas = 7; // launch_decode_salvage: marks, segments, interval scans, their results, lengths, status, (p, q)
 struct WorkAreas
 {
-    DeviceBuffer pipeline, plane, pack, interval[kIntervalArenas], seek[kSeekArenas];
+    DeviceBuffer pipeline, plane, pack, interval[kIntervalArenas], seek[kSeekArenas], salvage[kSalvageArenas];
     PipelineLanes lanes;
     size_t bytes() const noexcept
     {
@@ -585,6 +621,8 @@ struct WorkAreas
         for (const DeviceBuffer& b : interval)
             total += b.capacity();
         for (const DeviceBuffer& b : seek)
+            total += b.capacity();
+        for (const DeviceBuffer& b : salvage)
             total += b.capacity();
         return total;
     }
@@ -596,6 +634,8 @@ struct WorkAreas
         for (DeviceBuffer& b : interval)
             b.release();
         for (DeviceBuffer& b : seek)
+            b.release();
+        for (DeviceBuffer& b : salvage)
             b.release();
     }
 };
@@ -662,6 +702,55 @@ void launch_decode_intervals(const ScanDesc& proto, const ScanDesc* d_descs, Sca
             launch_decode_plain(proto, d_descs + i, d_results + i, 1, stream);
 }
 } // namespace
+
+// All `count` scans share proto's geometry and restart interval (salvage_launch_key).  The intervals of every scan are found
+// by their markers as far as these can be trusted, decoded as scans of their own by the ordinary decoders -- the exact decoder's
+// one launch settles what the speed path leaves undecided -- and judged; the rows of the intervals that are not kept are filled.
+void launch_decode_salvage(const ScanDesc& proto, const ScanDesc* d_descs, uint32_t count, const SalvageOutputs& outputs,
+                           hipStream_t stream)
+{
+    if (count == 0)
+        return;
+    const uint32_t lines = proto.restart_interval;
+    const uint32_t intervals = (proto.height + lines - 1) / lines;
+    const uint32_t max_marks = intervals + 7;
+    const size_t subs_n = static_cast<size_t>(count) * intervals;
+    DeviceBuffer* arena = areas().salvage;
+    auto* d_marks = static_cast<uint32_t*>(arena[0].ensure(with_headroom(sizeof(uint32_t) * count * max_marks)));
+    auto* d_segments = static_cast<salvage::Segment*>(arena[1].ensure(with_headroom(sizeof(salvage::Segment) * count)));
+    auto* d_subs = static_cast<ScanDesc*>(arena[2].ensure(with_headroom(sizeof(ScanDesc) * subs_n)));
+    auto* d_sub_results = static_cast<ScanResult*>(arena[3].ensure(with_headroom(sizeof(ScanResult) * subs_n)));
+    auto* d_expect = static_cast<uint64_t*>(arena[4].ensure(with_headroom(sizeof(uint64_t) * subs_n)));
+    auto* d_status = static_cast<uint8_t*>(arena[5].ensure(with_headroom(subs_n)));
+    auto* d_counts = static_cast<uint32_t*>(arena[6].ensure(with_headroom(sizeof(uint32_t) * 2 * count)));
+    hipLaunchKernelGGL(salvage::find_salvage_markers, dim3(count), dim3(64), 0, stream, d_descs, d_marks, max_marks, d_segments);
+    hip_check(hipGetLastError());
+    hipLaunchKernelGGL(salvage::plan_salvage, dim3(count), dim3(64), 0, stream, d_descs, static_cast<const uint32_t*>(d_marks), max_marks,
+                       static_cast<const salvage::Segment*>(d_segments), intervals, d_subs, d_expect, d_status, d_counts);
+    hip_check(hipGetLastError());
+    ScanDesc sub_proto = proto;
+    sub_proto.height = lines;
+    sub_proto.restart_interval = 0;
+    launch_decode_plain(sub_proto, d_subs, d_sub_results, static_cast<uint32_t>(subs_n), stream);
+    const uint64_t row_bytes = static_cast<uint64_t>(proto.width) * (proto.interleave_mode == 0 ? 1 : proto.components) *
+                               (proto.bits_per_sample > 8 ? 2 : 1);
+    for (uint32_t first = 0; first < count; first += 65535u) // (a grid has at most 65535 rows)
+    {
+        const size_t at = static_cast<size_t>(first) * intervals;
+        hipLaunchKernelGGL(salvage::judge_and_fill, dim3(intervals, std::min(count - first, 65535u)), dim3(salvage::kFillThreads), 0, stream,
+                           d_descs + first, intervals, static_cast<const ScanResult*>(d_sub_results + at),
+                           static_cast<const uint64_t*>(d_expect + at), d_status + at, outputs.fill_value,
+                           proto.bits_per_sample > 8 ? 1u : 0u, row_bytes);
+        hip_check(hipGetLastError());
+    }
+    g_salvage_launches.fetch_add(3);
+    std::vector<salvage::Segment> segments(count);
+    hip_check(hipMemcpyAsync(outputs.status, d_status, subs_n, hipMemcpyDeviceToHost, stream));
+    hip_check(hipMemcpyAsync(segments.data(), d_segments, sizeof(salvage::Segment) * count, hipMemcpyDeviceToHost, stream));
+    hip_check(hipStreamSynchronize(stream));
+    for (uint32_t i = 0; i < count; ++i)
+        outputs.segment_ends[i] = segments[i].end;
+}
 
 void launch_decode(const ScanDesc& proto, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
                    hipStream_t stream)

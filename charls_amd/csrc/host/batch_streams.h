@@ -35,6 +35,13 @@ void decode_batch_streams(uint32_t frame_count, const void* d_streams, const uin
                           void* d_frames, size_t frame_pitch_bytes, uint32_t stride_arg, charls_amd_codec_params* params_out,
                           charls_jpegls_errc* errcs, void* hip_stream);
 
+// charls_amd_decode_batch_device_salvage (batch_salvage.cpp; the part-1 call of the same name hands over ONE frame): the
+// ragged decode above, then the salvage round for the frames it failed on.  frame_count >= 1, pointers checked by the caller.
+void decode_batch_salvage(uint32_t frame_count, const void* d_packed, const uint64_t* offsets, const uint64_t* sizes,
+                          const charls_amd_frame_dest* dests, uint32_t fill_value, charls_amd_codec_params* params_out,
+                          charls_amd_salvage_report* reports, uint8_t* interval_status, size_t status_pitch_bytes,
+                          charls_jpegls_errc* errcs, void* hip_stream);
+
 // The batch encoder behind charls_amd_encode_batch_device with every frame's pixels named by a pointer of its own
 // (d_pixels: HOST array of frame_count DEVICE pointers; the slot call passes d_frames + i * frame_pitch_bytes): frame i's
 // .jls goes to d_streams + i * stream_pitch_bytes.  `frame_bytes` is what every frame offers from its pointer on (the slot

@@ -2,10 +2,12 @@
 //
 // Same state machine, checks and error codes as the reference facade (src/charls_jpegls_decoder.cpp:21-533); the scan
 // itself (`make_scan_codec<scan_decoder>()->decode_scan`, :186-189) runs on the GPU through ScanEngine.
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <vector>
 
+#include "batch_streams.h"
 #include "common.h"
 #include "scan_engine.h"
 #include "seek_index.h"
@@ -242,8 +244,57 @@ struct charls_jpegls_decoder
         state = State::completed;
     }
 
+    // decode_to_buffer, and where it fails the salvage round of part 2g on this one frame.  Raises what decode raises.
+    void decode_salvaging(void* destination, size_t size, size_t stride_arg, uint32_t fill_value, charls_amd_salvage_report& report,
+                          uint8_t* interval_status, size_t status_capacity)
+    {
+        check_buffer(destination, size);
+        check_operation(state == State::header_read);
+        const StreamReader header = reader; // (as read: behind the first scan's header)
+        report = charls_amd_salvage_report{0, 0, 0, 0, UINT32_MAX, 0};
+        try
+        {
+            decode(destination, size, stride_arg);
+        }
+        catch (const error&)
+        {
+            try
+            {
+                salvage(header, destination, size, stride_arg, fill_value, report, interval_status, status_capacity);
+            }
+            catch (const error&)
+            { // (nothing salvaged; the call reports what decode_to_buffer reports)
+                report.state = 0;
+            }
+            if (report.state != 1) // (whatever a second decode made of the frame: the first one failed, nothing is handed out)
+                report = charls_amd_salvage_report{2, 0, 0, 0, UINT32_MAX, 0};
+            throw;
+        }
+    }
+
+    // The whole source goes to the handle's device buffers, the batch routine (batch_salvage.cpp) runs on that one frame, and
+    // the rows of a salvaged frame come back.  `header`: the reader as it stood behind the first scan's header.
+    void salvage(const StreamReader& header, void* destination, size_t size, size_t stride_arg, uint32_t fill_value,
+                 charls_amd_salvage_report& report, uint8_t* interval_status, size_t status_capacity)
+    {
+        const auto [row, stride] = row_and_stride(header, stride_arg);
+        const size_t rows = static_cast<size_t>(header.frame_info().height) * scans_of_frame(header);
+        if (stride < row || size < stride * rows - (stride - row))
+            return; // (what decode refused the destination for)
+        const ScanEngine::Staged staged = engine.stage_whole_stream(source, source_size, row * rows);
+        const uint64_t offset = 0, bytes = source_size;
+        const charls_amd_frame_dest dest{staged.d_pixels, row * rows, 0, 0}; // (device rows are packed)
+        charls_jpegls_errc errc{};
+        decode_batch_salvage(1, staged.d_stream, &offset, &bytes, &dest, fill_value, nullptr, &report, interval_status,
+                             interval_status != nullptr ? std::max<size_t>(status_capacity, 1) : 0, &errc, staged.stream);
+        if (report.state == 1)
+            engine.fetch_staged_rows(static_cast<uint8_t*>(destination), stride, row, rows);
+    }
+
     State state{State::initial};
     StreamReader reader;
+    const uint8_t* source{}; // as given to set_source_buffer
+    size_t source_size{};
     ScanEngine engine;
     // the seek-point index (seek_index.h): the one set_index gave, or the one a decode_to_buffer_and_index collects
     IndexMode index_mode{IndexMode::none};
@@ -278,6 +329,8 @@ charls_jpegls_errc charls_jpegls_decoder_set_source_buffer(charls_jpegls_decoder
     check_buffer(source, size);
     check_operation(d->state == D::State::initial);
     d->reader.set_source(static_cast<const uint8_t*>(source), size);
+    d->source = static_cast<const uint8_t*>(source);
+    d->source_size = size;
     d->state = D::State::source_set;
     d->engine.expect_call(true); // (the read_header / decode_to_buffer calls of this thread follow: others about to launch wait for them)
     JLS_THUNK_END
@@ -377,6 +430,20 @@ charls_jpegls_errc charls_jpegls_decoder_decode_to_buffer(charls_jpegls_decoder*
         ~Reset() { d->index_mode = IndexMode::none; }
     } reset{d};
     d->decode(destination, size, stride);
+    JLS_THUNK_END
+}
+
+charls_jpegls_errc charls_amd_jpegls_decoder_decode_to_buffer_salvage(charls_jpegls_decoder* d, void* destination, size_t size,
+                                                                      uint32_t stride, uint32_t fill_value,
+                                                                      charls_amd_salvage_report* report, uint8_t* interval_status,
+                                                                      size_t status_capacity)
+{
+    JLS_THUNK_BEGIN
+    check_pointer(d);
+    check_pointer(report);
+    check_buffer(interval_status, status_capacity);
+    d->index_mode = IndexMode::none; // (launches on its own, from the top)
+    d->decode_salvaging(destination, size, stride, fill_value, *report, interval_status, status_capacity);
     JLS_THUNK_END
 }
 

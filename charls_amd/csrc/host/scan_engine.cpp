@@ -665,6 +665,21 @@ void ScanEngine::upload_stream(const uint8_t* source, size_t bytes, uint64_t hin
         trace_.upload_ms += now_ms() - t0, trace_.begin_ms = trace_.begin_ms == 0 ? t0 : trace_.begin_ms;
 }
 
+ScanEngine::Staged ScanEngine::stage_whole_stream(const uint8_t* source, size_t bytes, size_t pixel_bytes)
+{
+    ensure_stream();
+    r_->bits.ensure(bytes + 16); // (whole 16-byte groups are read)
+    r_->pixels.ensure(pixel_bytes);
+    stream_bytes_ = bytes;
+    hip_check(hipMemcpyAsync(r_->bits.as<uint8_t>(), source, bytes, hipMemcpyHostToDevice, r_->stream));
+    return Staged{r_->bits.as<uint8_t>(), r_->pixels.as<uint8_t>(), r_->stream};
+}
+
+void ScanEngine::fetch_staged_rows(uint8_t* destination, size_t stride, size_t row_bytes, size_t rows)
+{
+    copy_rows_out(destination, stride, r_->pixels.as<uint8_t>(), row_bytes, rows);
+}
+
 size_t ScanEngine::decode_scan(const ScanSpec& spec, size_t stream_offset, uint8_t* destination, size_t stride)
 {
     ensure_stream();

@@ -137,6 +137,18 @@ public:
     void decode_scan_band(const ScanSpec& spec, size_t stream_offset, uint8_t* destination, size_t stride, uint32_t first_row,
                           uint32_t rows, uint32_t lines, const uint8_t* points);
 
+    // ---- salvage decode (charls_amd_jpegls_decoder_decode_to_buffer_salvage; body in decoder_api.cpp's caller): the whole
+    // source stream in the handle's device buffer and room for the frame's packed rows beside it.  Launches on its own, like
+    // the indexed calls.
+    struct Staged
+    {
+        uint8_t* d_stream;
+        uint8_t* d_pixels;
+        hipStream_t stream;
+    };
+    Staged stage_whole_stream(const uint8_t* source, size_t bytes, size_t pixel_bytes);
+    void fetch_staged_rows(uint8_t* destination, size_t stride, size_t row_bytes, size_t rows);
+
     // A coding call is coming on this handle: announced to the coalescer, so that calls of other threads that are about to
     // launch a batch this one can join wait for it (coalescer.h).  Before the coding call (the decoder was given its source,
     // the encoder its frame info -- the caller may never code anything) the announcement counts for a millisecond; inside it

@@ -681,6 +681,75 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_encode_batch_device_budget(
     uint32_t offset_alignment, uint64_t* offsets, uint64_t* sizes, int32_t* near_out, charls_jpegls_errc* errcs, void* hip_stream);
 CHARLS_AMD_API int32_t charls_amd_measure_counters(uint64_t* out, int32_t capacity);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Part 2g -- SALVAGE decode: restart intervals confine damage.  charls_amd_decode_batch_device_ragged fails a frame as a
+ * whole when one byte of it is damaged; a frame coded with a restart interval (DRI) consists of intervals that decode on
+ * their own, and this call gives back the ones that are intact.  `reports` is a HOST array of frame_count elements,
+ * `interval_status` a HOST array (may be NULL); everything else is the ragged call's.
+ *
+ * Round 1 is charls_amd_decode_batch_device_ragged, unchanged: the return value, params_out[f], errcs[f] and the pixels of
+ *   every frame with errcs[f] == 0 are exactly that call's, for every input, and such a frame gets state 0.  A batch without
+ *   failed frames launches nothing else (charls_amd_salvage_counters does not move).  Errors of the whole call are those of
+ *   the ragged call and, checked before a device is asked for, `reports` == NULL and `interval_status` != NULL with
+ *   status_pitch_bytes == 0.  frame_count == 0 is success.
+ * Round 2 takes a frame with errcs[f] != 0 whose header was read and whose first scan was located, that passed its stride and
+ *   capacity checks, and whose first scan has a restart interval below the frame's height, at most 65535 rows, and is a scan
+ *   the interval-parallel decoder takes.  Every other failed frame gets state 2, counts of 0, and nothing is
+ *   promised about its destination, as before.  errcs[f] stays what round 1 said -- state 1 is how a caller learns that the
+ *   destination is usable -- with one exception: a fill_value above the frame's MAXVAL makes errcs[f] invalid_argument for a
+ *   frame that would have been salvaged (state 2).
+ * The segment of scan c runs from behind its SOS header to the first FF xx with xx >= 0x80 that is no FF D0..D7, or to the
+ *   end of the source.  The markers FF D0+n inside it, m_0 .. m_{M-1} with numbers n_k, cut it into the pieces
+ *   P_0 = [0, m_0), P_k = [m_{k-1} + 2, m_k), P_M = [m_{M-1} + 2, end).  N = ceil(height / Ri).  At most N + 7 markers are
+ *   recorded; with more, the recorded ones count as all of them and q = 0.
+ * Which piece is which interval -- never by guessing how many markers were lost:
+ *   forward: p is the largest p <= min(M, N - 1) with n_k == k mod 8 for all k < p; piece k < p claims interval k.
+ *   backward: q is the largest q <= min(M, N - 1) with n_{M-1-t} == (N - 2 - t) mod 8 for all t < q; piece M - t, t < q,
+ *   claims interval N - 1 - t.  A piece with two different claims claims nothing; an interval claimed by two different pieces
+ *   is claimed by none.  (Eight markers lost in a row cannot be seen in the 3-bit numbers: every piece between then has two
+ *   claims, and nothing is misplaced.)
+ * A claimed piece is decoded as an independent scan of that interval's rows.  The interval is KEPT if and only if the scan
+ *   ends without error, leaves no decision open and consumed exactly the piece's bytes.  Every other interval is LOST: its
+ *   rows get fill_value as the sample value of every component (16-bit samples little-endian), after the decoders have run.
+ *   This is deliberately stricter than the reference's reader, which skips a pad byte or FF fill bytes in front of a marker:
+ *   a piece that ends that way is lost here.  It only ever applies to frames that failed round 1.  Damage that decodes
+ *   cleanly to the piece's exact length cannot be seen by anyone, here or in the reference.
+ * Later scans of a planar frame: scan c + 1 is looked for where scan c's segment ends; if no valid SOS of a scan of the same
+ *   kind is there, every interval of the scans not reached is lost and filled.
+ * interval_status + f * status_pitch_bytes holds one byte per (scan, interval) of a salvaged frame, scan-major: 0 kept,
+ *   1 no piece claimed the interval, 2 the piece did not decode to its exact length, 3 the scan was not reached.  A
+ *   status_pitch_bytes below scans x N leaves that frame's status unwritten and sets reports[f].reserved to 1; the pixels
+ *   and the report are valid all the same.
+ * Nothing is written outside the rows of a frame's own destination; one frame's damage never changes another frame's result.
+ * charls_amd_jpegls_decoder_decode_to_buffer_salvage: the same for one stream in host memory, after read_header.  It returns
+ *   what charls_jpegls_decoder_decode_to_buffer returns; where that is an error and the report says state 1, `destination`
+ *   holds the salvaged frame.  interval_status (may be NULL) has room for status_capacity bytes.  It launches on its own and
+ *   stages through the handle's device buffers.
+ * charls_amd_last_timings after the batch call: [0], [1] as after the ragged call; where a round 2 ran, [2] is the time that
+ *   round took in ms by the host's clock (each of its launches ends in a synchronise).
+ * salvage_counters: out[0] frames salvaged, out[1] intervals kept, out[2] intervals lost, out[3] launches of the salvage
+ *   kernels; process-wide since load; returns the number of values written (4 at most).
+ * Not done: streams without restart intervals, partial intervals, the slot, indexed and multi-device calls.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct charls_amd_salvage_report
+{
+    uint32_t state;          /* 0 decoded whole; 1 salvaged; 2 failed and nothing salvaged */
+    uint32_t intervals;      /* restart intervals of the frame, summed over its scans (state 1; else 0) */
+    uint32_t intervals_lost;
+    uint32_t rows_lost;      /* rows filled, summed over scans (a planar frame counts each plane's rows) */
+    uint32_t first_lost_row; /* lowest row of the frame that holds fill in any scan; UINT32_MAX: none */
+    uint32_t reserved;       /* written as 0 (1: status_pitch_bytes was too small for this frame) */
+} charls_amd_salvage_report;
+
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_device_salvage(
+    uint32_t frame_count, const void* d_packed, const uint64_t* offsets, const uint64_t* sizes, const charls_amd_frame_dest* dests,
+    uint32_t fill_value, charls_amd_codec_params* params_out, charls_amd_salvage_report* reports, uint8_t* interval_status,
+    size_t status_pitch_bytes, charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_jpegls_decoder_decode_to_buffer_salvage(
+    charls_jpegls_decoder* decoder, void* destination, size_t size, uint32_t stride, uint32_t fill_value,
+    charls_amd_salvage_report* report, uint8_t* interval_status, size_t status_capacity);
+CHARLS_AMD_API int32_t charls_amd_salvage_counters(uint64_t* out, int32_t capacity);
+
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */
 CHARLS_AMD_API charls_jpegls_errc charls_amd_set_encode_engine(int32_t engine);
