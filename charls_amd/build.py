@@ -17,10 +17,14 @@ OUT_ALIAS = os.path.join(OUT_DIR, "libcharls.so.3")
 VERSION_SCRIPT = os.path.join(CSRC, "charls_amd.version")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-# translation units; the *.hip kernel sources are #included by the launch code that instantiates them (runtime.hip, and
-# units of their own, one per sample width, for the kernels with the most instantiations, so that the build stays parallel)
+# translation units; every *.hip kernel source is #included by exactly one unit, the launch code that instantiates it:
+# runtime.hip (serial and container kernels), decode_launch.hip and encode_launch.hip (the decoder and encoder dispatch),
+# and units of their own, one per sample width and form, for the kernels with the most instantiations, so that the build
+# stays parallel
 SOURCES = [
     "device/runtime.hip",
+    "device/decode_launch.hip",
+    "device/encode_launch.hip",
     "device/launch_pixels_u8.hip",
     "device/launch_pixels_u16.hip",
     "device/launch_group_encode_u8.hip",
@@ -55,18 +59,37 @@ LLVM_BIN = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 OFFLOAD_ARCH = "gfx950"  # the one target of this library (also the bundle id the scratch check unpacks)
 
 
+BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
+def device_code_objects(path: str, tmp: str) -> list[str]:
+    """The gfx950 code objects of a hipcc object -- or of the linked library, which holds one bundle per translation unit --
+    cut out of its .hip_fatbin section and written into the directory `tmp`."""
+    fat = os.path.join(tmp, "fat.bin")
+    subprocess.check_call([os.path.join(LLVM_BIN, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, path])
+    if not os.path.exists(fat) or os.path.getsize(fat) == 0:
+        return []
+    with open(fat, "rb") as f:
+        data = f.read()
+    outs = []
+    for i, piece in enumerate(data.split(BUNDLE_MAGIC)[1:]):
+        bundle, dev = os.path.join(tmp, f"bundle{i}.bin"), os.path.join(tmp, f"dev{i}.co")
+        with open(bundle, "wb") as f:
+            f.write(BUNDLE_MAGIC + piece)
+        subprocess.check_call([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + bundle,
+                               "--targets=hipv4-amdgcn-amd-amdhsa--" + OFFLOAD_ARCH, "--output=" + dev])
+        if os.path.getsize(dev) != 0:
+            outs.append(dev)
+    return outs
+
+
 def kernel_resources(obj: str) -> list[dict]:
-    """Kernels of one hipcc object with what their code-object notes say about them: name, private segment (scratch) bytes,
-    VGPRs, SGPRs, static LDS.  The gfx950 code object is cut out of the object's .hip_fatbin section."""
+    """Kernels of one hipcc object (or of the linked library) with what their code-object notes say about them: name, private
+    segment (scratch) bytes, VGPRs, SGPRs, static LDS."""
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
-        fat, dev = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "dev.co")
-        subprocess.check_call([os.path.join(LLVM_BIN, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj])
-        if not os.path.exists(fat) or os.path.getsize(fat) == 0:
-            return []
-        subprocess.check_call([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--" + OFFLOAD_ARCH, "--output=" + dev])
-        notes = subprocess.check_output([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", dev]).decode()
+        notes = "".join(subprocess.check_output([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", dev]).decode()
+                        for dev in device_code_objects(obj, tmp))
     kernels, cur = [], None
     keys = {".private_segment_fixed_size": "scratch", ".vgpr_count": "vgprs", ".sgpr_count": "sgprs",
             ".group_segment_fixed_size": "lds", ".name": "name"}
@@ -154,7 +177,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     # An object is compiled again when anything it can include is newer: the device units include device/, host/common.h
     # (through runtime.h) and the public header it includes; the host units host/, the headers of device/ and the public
     # header (a change to a kernel does not recompile the facade, a change to the facade's sources not the kernels -- the
-    # five device units take minutes).  `force` compiles everything.
+    # device units take minutes).  `force` compiles everything.
     def newest(paths):
         return max(os.path.getmtime(f) for f in paths if os.path.isfile(f))
     device_files = glob.glob(os.path.join(CSRC, "device", "*"))

@@ -1,27 +1,33 @@
-// launch_group_encode.inc -- launches of encode_pixels_group (scan_group_encode.hip); see group_launch.h.  Compiled for
-// gfx950 only.
+// launch_group_encode.inc -- launches of encode_pixels_group (scan_group_encode.hip) in its encoding form, or, with
+// JLS_UNIT_MEASURE, in its measuring form (kMeasure); see group_launch.h.  Compiled for gfx950 only.
 #include <hip/hip_runtime.h>
-
-#if JLS_LAUNCH_WIDE
-#define JLS_LAUNCH_SAMPLE uint16_t
-#define JLS_LAUNCH_NAME launch_encode_group_wide
-#else
-#define JLS_LAUNCH_SAMPLE uint8_t
-#define JLS_LAUNCH_NAME launch_encode_group_narrow
-#endif
 
 #include "group_launch.h"
 #include "scan_group_encode.hip"
 
-// Included by launch_group_encode_u8.hip and launch_group_encode_u16.hip: one translation unit per sample width.
+// Included by launch_group_encode_u8/_u16.hip and launch_group_measure_u8/_u16.hip: one translation unit per sample width
+// and form (JLS_UNIT_WIDE, JLS_UNIT_MEASURE).
 namespace jls::dev {
 
-void launch_encode_group_narrow(const ScanDesc& proto, int lanes, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
-                         hipStream_t stream);
-void launch_encode_group_wide(const ScanDesc& proto, int lanes, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
-                         hipStream_t stream);
+namespace {
+using LaunchSample = std::conditional_t<JLS_UNIT_WIDE != 0, uint16_t, uint8_t>;
+constexpr bool kLaunchMeasure = JLS_UNIT_MEASURE != 0;
+} // namespace
 
-#if JLS_LAUNCH_WIDE == 0
+template <typename S, bool kMeasure>
+void launch_encode_group_as(const ScanDesc& proto, int lanes, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
+                            hipStream_t stream);
+// (each of the four units defines one of these)
+template <>
+void launch_encode_group_as<uint8_t, false>(const ScanDesc&, int, const ScanDesc*, ScanResult*, uint32_t, hipStream_t);
+template <>
+void launch_encode_group_as<uint16_t, false>(const ScanDesc&, int, const ScanDesc*, ScanResult*, uint32_t, hipStream_t);
+template <>
+void launch_encode_group_as<uint8_t, true>(const ScanDesc&, int, const ScanDesc*, ScanResult*, uint32_t, hipStream_t);
+template <>
+void launch_encode_group_as<uint16_t, true>(const ScanDesc&, int, const ScanDesc*, ScanResult*, uint32_t, hipStream_t);
+
+#if JLS_UNIT_WIDE == 0 && JLS_UNIT_MEASURE == 0
 size_t group_encode_lds_bytes(const ScanDesc& d, uint32_t scans_per_wave)
 {
     const uint32_t nc = d.interleave_mode == 2 ? static_cast<uint32_t>(d.components) : 1u;
@@ -33,70 +39,44 @@ size_t group_encode_lds_bytes(const ScanDesc& d, uint32_t scans_per_wave)
 void launch_encode_group(const ScanDesc& proto, int lanes, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
                          hipStream_t stream)
 {
-    if (proto.bits_per_sample > 8)
-        launch_encode_group_wide(proto, lanes, d_descs, d_results, count, stream);
-    else
-        launch_encode_group_narrow(proto, lanes, d_descs, d_results, count, stream);
+    dispatch_sample(proto.bits_per_sample, [&](auto s) {
+        launch_encode_group_as<typename decltype(s)::type, false>(proto, lanes, d_descs, d_results, count, stream);
+    });
+}
+
+void launch_measure_group(const ScanDesc& proto, int lanes, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
+                          hipStream_t stream)
+{
+    dispatch_sample(proto.bits_per_sample, [&](auto s) {
+        launch_encode_group_as<typename decltype(s)::type, true>(proto, lanes, d_descs, d_results, count, stream);
+    });
 }
 #endif
 
-void JLS_LAUNCH_NAME(const ScanDesc& proto, int lanes, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
-                         hipStream_t stream)
+// (the regions in LDS are those of the encoding form: one layout for both)
+template <>
+void launch_encode_group_as<LaunchSample, kLaunchMeasure>(const ScanDesc& proto, int lanes, const ScanDesc* d_descs,
+                                                          ScanResult* d_results, uint32_t count, hipStream_t stream)
 {
+    using S = LaunchSample;
     const uint32_t per_wave = 64u / static_cast<uint32_t>(lanes);
     const dim3 grid((count + per_wave - 1) / per_wave);
     const size_t lds = group_encode_lds_bytes(proto, per_wave);
     const int nc = proto.interleave_mode == 2 ? proto.components : 1;
-#define JLS_LAUNCH_ENCODE(S, G, N)                                                                                       \
-    do                                                                                                                   \
-    {                                                                                                                    \
-        if (lds > kMaxDynamicLds)                                                                                        \
-            hip_check(hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_pixels_group<S, G, N>),                  \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));           \
-        hipLaunchKernelGGL((encode_pixels_group<S, G, N>), grid, dim3(64), lds, stream, d_descs, d_results, count);      \
-    } while (0)
-#define JLS_LAUNCH_ENCODE_L(S, G, NLINES)                                                                                \
-    do                                                                                                                   \
-    {                                                                                                                    \
-        if (lds > kMaxDynamicLds)                                                                                        \
-            hip_check(hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_pixels_group<S, G, 1, NLINES>),          \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));           \
-        hipLaunchKernelGGL((encode_pixels_group<S, G, 1, NLINES>), grid, dim3(64), lds, stream, d_descs, d_results, count); \
-    } while (0)
-#define JLS_LAUNCH_ENCODE_N(S, G)                                                                                        \
-    do                                                                                                                   \
-    {                                                                                                                    \
-        if (proto.interleave_mode == 1)                                                                                  \
-        {                                                                                                                \
-            if (proto.components == 2) JLS_LAUNCH_ENCODE_L(S, G, 2);                                                     \
-            else if (proto.components == 3) JLS_LAUNCH_ENCODE_L(S, G, 3);                                                \
-            else JLS_LAUNCH_ENCODE_L(S, G, 4);                                                                           \
-        }                                                                                                                \
-        else if (nc == 1) JLS_LAUNCH_ENCODE(S, G, 1);                                                                    \
-        else if (nc == 2) JLS_LAUNCH_ENCODE(S, G, 2);                                                                    \
-        else if (nc == 3) JLS_LAUNCH_ENCODE(S, G, 3);                                                                    \
-        else JLS_LAUNCH_ENCODE(S, G, 4);                                                                                 \
-    } while (0)
-    if (lanes == 8)
-    {
-        JLS_LAUNCH_ENCODE_N(JLS_LAUNCH_SAMPLE, 8);
-    }
-    else if (lanes == 16)
-    {
-        JLS_LAUNCH_ENCODE_N(JLS_LAUNCH_SAMPLE, 16);
-    }
-    else if (lanes == 32)
-    {
-        JLS_LAUNCH_ENCODE_N(JLS_LAUNCH_SAMPLE, 32);
-    }
-    else
-    {
-        JLS_LAUNCH_ENCODE_N(JLS_LAUNCH_SAMPLE, 64);
-    }
-#undef JLS_LAUNCH_ENCODE_N
-#undef JLS_LAUNCH_ENCODE_L
-#undef JLS_LAUNCH_ENCODE
-    hip_check(hipGetLastError());
+    // one line of NC co-sited components (sample interleave, single component), or NL lines of one component (line interleave)
+    dispatch_int<8, 16, 32, 64>(lanes, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        if (proto.interleave_mode == 1)
+            dispatch_int<2, 3, 4>(proto.components, [&](auto nl) {
+                launch_kernel(encode_pixels_group<S, G, 1, decltype(nl)::value, kLaunchMeasure>, grid, dim3(64), lds, stream, d_descs,
+                              d_results, count);
+            });
+        else
+            dispatch_int<1, 2, 3, 4>(nc, [&](auto n) {
+                launch_kernel(encode_pixels_group<S, G, decltype(n)::value, 1, kLaunchMeasure>, grid, dim3(64), lds, stream, d_descs,
+                              d_results, count);
+            });
+    });
 }
 
 } // namespace jls::dev

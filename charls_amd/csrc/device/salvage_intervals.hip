@@ -1,6 +1,6 @@
 // salvage_intervals.hip -- restart intervals as the unit that CONFINES DAMAGE (charls_amd.h part 2g; host/batch_salvage.cpp).
 //
-// restart_intervals.hip decodes the intervals of a sound scan side by side and hands anything irregular to the sequential
+// restart_intervals_decode.hip decodes the intervals of a sound scan side by side and hands anything irregular to the sequential
 // decoder, which reports the reference's error for the whole frame.  The kernels here serve frames that already failed that
 // way: they say which stretch of a damaged entropy-coded segment is which interval, let the ordinary decoders run on those
 // stretches as scans of their own, keep the intervals that decode to exactly their length and fill the rest.

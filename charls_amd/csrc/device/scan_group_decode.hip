@@ -19,11 +19,11 @@
 //     (a lane's 16 bytes as one 128-bit number: refill), preparing what the steps need of the previous line 64 samples ahead
 //     (prepare), run fills, and the 16-byte row stores of every finished line;
 //   * LDS per scan: 365 context records (8 B), two run contexts, a 1 KB dense bit ring, 192 prepared entries (8 B) and ONE line
-//     of samples = 9.7 KB for 4096 8-bit samples (the launch rule: runtime.hip, decode_group_plan).
+//     of samples = 9.7 KB for 4096 8-bit samples (the launch rule: decode_launch.hip, decode_group_plan).
 //
 // Like scan_fast_decode.hip this is not a restatement of the reference's bit reader: a result is accepted only when the
 // scan ends cleanly (all samples decoded inside the entropy-coded segment, zero padding, marker next); everything else
-// reports flags = kFastRetry and the exact decoder decides (runtime.hip: launch_decode_plain).
+// reports flags = kFastRetry and the exact decoder decides (decode_launch.hip: launch_decode_plain).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -89,7 +89,7 @@ struct HashJob
 #ifdef __HIPCC__
 namespace jls::dev {
 
-// decode_scans_wave's conditions (runtime.hip: wave_decode_eligible) and no restart intervals.
+// decode_scans_wave's conditions (decode_launch.hip: wave_decode_eligible) and no restart intervals.
 bool seek_decode_eligible(const ScanDesc& d) noexcept;
 // One scan per wavefront, as decode_scans_wave, writing the seek points of scan s from d_points + s * scan_stride.
 void launch_seek_emit(const ScanDesc& proto, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count, uint8_t* d_points,

@@ -245,7 +245,7 @@ def coded(name) -> CodedCorner:
 
 # ---- which frames go to which coding route -------------------------------------------------------------------------------
 #
-# What a route can take is what charls_amd/csrc/device/runtime.hip says of it (wave_decode_eligible, fast_decode_eligible,
+# What a route can take is what charls_amd/csrc/device/decode_launch.hip and encode_launch.hip say of it (wave_decode_eligible, fast_decode_eligible,
 # pixel_group_lanes, pipeline_eligible); tests/test_gpu_corners.py sends every frame of ROUTES through its route,
 # tests/test_emu_corners.py the frames of EMU_ROUTES (taken in turn where several kernels share them), and
 # tests/test_corner_census_cpu.py asserts from the census that the frames of a route reach every corner that can occur on it.

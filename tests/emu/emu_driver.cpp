@@ -35,7 +35,7 @@ void emu_decode_scans_serial(const jls::ScanDesc* descs, jls::ScanResult* result
     emu::launch(jls::decode_scans_serial, dim3(count), dim3(64), 0, descs, results);
 }
 
-// NC co-sited components / sample width chosen exactly as the host dispatcher does (runtime.hip: launch_decode).
+// NC co-sited components / sample width chosen exactly as the host dispatcher does (decode_launch.hip: launch_decode).
 int emu_decode_scans_wave(const jls::ScanDesc* descs, jls::ScanResult* results, int count)
 {
     const jls::ScanDesc& d = descs[0];
@@ -96,7 +96,7 @@ void emu_stuff_raw(const uint8_t* raw, uint64_t total_bits, uint64_t raw_bytes, 
     d.stream = out;
     d.stream_capacity = capacity;
     if (blocks == 2)
-    { // the speculative form (speculative_stuffing.hip), grids as in runtime.hip
+    { // the speculative form (speculative_stuffing.hip), grids as in encode_launch.hip
         const unsigned waves = (unsigned)(raw_bytes / spec.chunk_bytes + 1);
         emu::launch(pipe::stuff_spec_survey, dim3(waves, 1), dim3(64), 0, (const pipe::Work*)&w, spec.chunk_bytes, spec.warm_bytes);
         emu::launch(pipe::stuff_spec_resolve, dim3(1), dim3(64), 0, (const pipe::Work*)&w, spec.chunk_bytes);
@@ -133,7 +133,7 @@ int emu_decode_scans_group(const jls::ScanDesc* descs, jls::ScanResult* results,
         else EMU_GROUP_N(S, G, 4);                          \
     } while (0)
     if (d.near_lossless != 0)
-    { // decode_scans_group<S, G, NL, 1, true>: the product's near-lossless instantiations (runtime.hip: launch_decode_plain)
+    { // decode_scans_group<S, G, NL, 1, true>: the product's near-lossless instantiations (decode_launch.hip: launch_decode_plain)
 #define EMU_GROUP_NEAR(S, G)                                                                                                              \
     do                                                                                                                                    \
     {                                                                                                                                     \
@@ -340,7 +340,7 @@ int emu_encode_pixels_group(const jls::ScanDesc* descs, jls::ScanResult* results
     return 0;
 }
 
-// restart_intervals.hip, decode side: marker search, interval descriptors, and (given the intervals' results) the check.
+// restart_intervals_decode.hip: marker search, interval descriptors, and (given the intervals' results) the check.
 void emu_find_restart_markers(const jls::ScanDesc* descs, uint32_t* marks, uint32_t max_marks, uint32_t* counts, int count)
 {
     emu::launch(jls::interval::find_restart_markers, dim3(count), dim3(64), 0, descs, marks, max_marks, counts);
@@ -369,7 +369,7 @@ void emu_join_intervals(const jls::ScanDesc* parents, const jls::ScanDesc* subs,
                 (const uint64_t*)offsets, (const jls::ScanResult*)results);
 }
 
-// The whole restart-interval encode of runtime.hip (launch_encode_intervals) for lossless scans, on the host: interval
+// The whole restart-interval encode of encode_launch.hip (launch_encode_intervals) for lossless scans, on the host: interval
 // descriptors, the pipeline on the intervals, the join.
 void emu_encode_with_restart_intervals(const jls::ScanDesc* parents, jls::ScanResult* results, int count, uint64_t capacity)
 {

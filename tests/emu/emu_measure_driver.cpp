@@ -14,7 +14,7 @@ extern "C" {
 
 size_t emu_sizeof_scan_desc() { return sizeof(jls::ScanDesc); }
 
-// Sample width, NC / NL and LDS chosen as dev::launch_measure_group does (launch_group_measure.inc); `group` lanes per scan.
+// Sample width, NC / NL and LDS chosen as dev::launch_measure_group does (launch_group_encode.inc); `group` lanes per scan.
 int emu_measure_pixels_group(const jls::ScanDesc* descs, jls::ScanResult* results, int count, int group)
 {
     const jls::ScanDesc& d = descs[0];

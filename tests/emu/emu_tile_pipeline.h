@@ -1,5 +1,5 @@
 // TEST-ONLY: the tile pipeline (tile_pipeline.hip, tile_pixel_mode.hip) on the host, kernel by kernel, in the order and with
-// the launch geometry runtime.hip uses.  Shared by the two emulator libraries (emu_tile_driver.cpp, emu_driver.cpp).
+// the launch geometry encode_launch.hip uses.  Shared by the two emulator libraries (emu_tile_driver.cpp, emu_driver.cpp).
 #pragma once
 #include "emu_launch.h"
 
@@ -14,7 +14,7 @@
 
 static uint32_t g_counters[jls::tile::kCounters]; // of the last emu_encode_tile_pipeline call
 
-// The tile pipeline (tile_pipeline.hip), kernel by kernel, in the order and with the launch geometry runtime.hip uses.
+// The tile pipeline (tile_pipeline.hip), kernel by kernel, in the order and with the launch geometry encode_launch.hip uses.
 // job_events / warm_events as given: the tests use small values so that small images have many jobs, and warm-ups too
 // short to converge so that settle_chains has to walk jobs again.
 template <typename S>
@@ -22,7 +22,7 @@ static void emu_tile_pipeline(const jls::ScanDesc* descs, jls::ScanResult* resul
                               uint32_t run_job_events, uint32_t run_warm_events, uint32_t run_long_warm_events)
 {
     using namespace jls;
-    job_events = std::max<uint32_t>(32, job_events / 32 * 32); // (whole rounds of the walkers, as runtime.hip rounds it)
+    job_events = std::max<uint32_t>(32, job_events / 32 * 32); // (whole rounds of the walkers, as encode_launch.hip rounds it)
     const ScanDesc& p = descs[0];
     const tile::TilePlan plan = tile::plan_tiles(p);
     const size_t samples = (size_t)plan.samples;

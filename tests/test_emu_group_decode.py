@@ -210,7 +210,7 @@ def test_group_decoder_defers_on_corrupt_streams(name):
 
 @pytest.mark.parametrize("bits,kind", [(8, "mixed"), (8, "zero"), (16, "mixed"), (12, "hard")])
 def test_group_dispatch_on_mutated_scan_data_matches_the_oracle(bits, kind):
-    """What runtime.hip's launch_decode_plain does (group kernel, then ONE launch of the exact wave decoder for the scans
+    """What decode_launch.hip's launch_decode_plain does (group kernel, then ONE launch of the exact wave decoder for the scans
     that reported kFastRetry) on a batch of mutated streams; every frame ends with the oracle's pixels or error code."""
     L = emu_bind.lib()
     w, h = 48, 12

@@ -1,4 +1,4 @@
-"""Kernel-logic check on the CPU for restart_intervals.hip (compiled for the host by tests/emu): the marker search on
+"""Kernel-logic check on the CPU for restart_intervals_decode.hip and restart_intervals_encode.hip (compiled for the host by tests/emu): the marker search on
 hand-made byte strings and on a reference fixture, interval descriptors, the acceptance check and the encode-side join."""
 import ctypes as C
 

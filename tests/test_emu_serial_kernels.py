@@ -202,7 +202,7 @@ def test_emulated_fast_decoder_defers_on_corrupt_streams(name):
     assert res[0].errc == 0 and res[0].flags == 4
 
 
-# ---- the decoder dispatch of runtime.hip (speed path, exact wave decoder on kFastRetry) on mutated streams -------------
+# ---- the decoder dispatch of decode_launch.hip (speed path, exact wave decoder on kFastRetry) on mutated streams -------------
 def _emulated_dispatch(L, jls, cont, scan):
     """What launch_decode does for a single-component lossless scan: returns (errc, pixels or None)."""
     pc = jls_container.validated_pc(cont.pc, cont.bits, 0)

@@ -210,7 +210,7 @@ def test_serial_decoder_rows(w, h, bits, comps, ilv, near, cls, base, pitch, tig
     _decode(_serial, G(w, h, bits, comps, ilv), cls, base, count=2, pitch=pitch, tight=tight, near=near, seed=w + comps, speed=False)
 
 
-# ---- restart_intervals.hip: the interval builders offset their sub-scans by j * lines * pixel_stride -------------------------
+# ---- restart_intervals_decode.hip, restart_intervals_encode.hip: the interval builders offset their sub-scans by j * lines * pixel_stride -------------------------
 
 @pytest.mark.parametrize("w,h,bits,comps,ilv,lines,cls,base", [(150, 10, 8, 1, 0, 4, "r16", 0), (7, 5, 8, 3, 1, 2, "p13", 1), (16, 7, 16, 1, 0, 3, "p2", 2),
                                                                (257, 3, 8, 3, 2, 1, "big", 8), (1, 4, 16, 1, 0, 2, "p1", 1), (16, 6, 8, 1, 0, 5, "r16p16", 0)])
@@ -237,7 +237,7 @@ def test_decode_interval_descriptors_follow_the_stride(w, h, bits, comps, ilv, l
                                                                      (16, 5, 8, 3, 2, 2, "p13", 2, False), (7, 6, 8, 3, 1, 4, "r16p16", 8, True),
                                                                      (150, 5, 16, 1, 0, 2, "p2", 2, False), (257, 3, 8, 1, 0, 2, "big", 0, False)])
 def test_restart_interval_encode_reads_padded_rows(w, h, bits, comps, ilv, lines, cls, base, tight):
-    """build_encode_intervals + the pipeline on the intervals + the join (runtime.hip: launch_encode_intervals): the joined
+    """build_encode_intervals + the pipeline on the intervals + the join (encode_launch.hip: launch_encode_intervals): the joined
     scan is the oracle's coding of every interval of the PACKED image with FF D0+m between them."""
     import oracle_bind as ob
     L = emu_bind.lib()

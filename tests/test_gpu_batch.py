@@ -152,7 +152,7 @@ def test_exact_decoder_agrees_with_speed_path(torch, knobs):
 @pytest.mark.parametrize("group,waves,bits,count,w,h", [(16, 4, 8, 37, 300, 40), (32, 4, 8, 5, 4096, 6), (32, 8, 16, 19, 129, 33), (16, 8, 12, 70, 64, 20),
                                                         (16, 4, 8, 1, 50, 50), (32, 4, 16, 64, 640, 24)])
 def test_decoder_workgroups_of_several_wavefronts(torch, knobs, group, waves, bits, count, w, h):
-    """decode_scans_group<S, G, 1, W>: the launch shape of big batches (one workgroup per CU, a wavefront per SIMD: runtime.hip,
+    """decode_scans_group<S, G, 1, W>: the launch shape of big batches (one workgroup per CU, a wavefront per SIMD: decode_launch.hip,
     decode_group_plan), forced here on small ones -- counts that leave wavefronts of the last workgroup without a scan, a single
     scan, a 4096-sample line -- and compared with the one-wavefront workgroups and the source frames."""
     frames = synth.frames_torch(count, w, h, seed0=90, bits=bits, kind="mixed", device="cuda:0")

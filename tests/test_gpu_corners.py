@@ -177,7 +177,7 @@ def _dri_scan(c, lines):
 @pytest.mark.parametrize("names", _restart_cases())
 def test_restart_intervals_both_ways(torch, lib, knobs, names):
     """Restart intervals of 5 lines: the encoder's intervals are the oracle's coding of each interval, the decoder gives the
-    oracle's pixels interval-parallel (restart_intervals.hip) and, SEQUENTIAL_INTERVALS = 1, with the scan left whole: the
+    oracle's pixels interval-parallel (restart_intervals_decode.hip) and, SEQUENTIAL_INTERVALS = 1, with the scan left whole: the
     speed path meets the RSTm and hands exactly these scans to the exact decoder."""
     lines = 5
     cs = [corners.CORPUS[n] for n in names]

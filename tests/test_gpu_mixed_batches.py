@@ -1,5 +1,5 @@
 """Batch decode of batches whose frames differ in their coding parameters (charls_amd.h part 2: every slot holds a complete
-.jls file and decodes as the part-1 decoder would decode it).  The launch key (runtime.hip: decode_launch_key) puts scans of
+.jls file and decodes as the part-1 decoder would decode it).  The launch key (decode_launch.hip: decode_launch_key) puts scans of
 one width, layout and sample type into one launch whose kernel is chosen from its first scan; a workgroup of the group
 decoder builds its gradient table from its own first scan, and everything the scans of a wavefront do not share in the step
 loop (RESET, the height) is per lane.  So each batch here is built frame by frame with the oracle (the product's encoder

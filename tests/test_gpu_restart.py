@@ -1,4 +1,4 @@
-"""Restart intervals as the parallel unit inside one scan (charls_amd/csrc/device/restart_intervals.hip).  GPU only.
+"""Restart intervals as the parallel unit inside one scan (charls_amd/csrc/device/restart_intervals.h).  GPU only.
 
 Decode side: streams with DRI/RSTm (the reference's fixtures and our own) are decoded interval-parallel; results and
 error codes must equal the sequential exact decoder's and the oracle's.

@@ -3,7 +3,7 @@
 The tile pipeline (DESIGN 4.1) codes every context chain and the run chain in JOBS that start from a guessed state;
 settle_chains / settle_runs check every job boundary and code a job again where the guess was wrong.  With the default
 job sizes and warm-ups nearly every guess is right on natural data, so the ordinary parity tests never execute the
-re-walks on the GPU.  Here the knobs (read per call, runtime.hip: TileLayout) make every boundary disagree -- jobs of 32
+re-walks on the GPU.  Here the knobs (read per call, encode_launch.hip: TileLayout) make every boundary disagree -- jobs of 32
 events with no warm-up -- and full-range noise, which never converges, goes through with the DEFAULT knobs.  The bytes must
 be the oracle's in every case, and charls_amd_speculation_counters must show that the re-walks really ran.
 

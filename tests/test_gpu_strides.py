@@ -6,7 +6,7 @@ checks of part 2.  Layout, canary check and geometry: tests/strided.py and the h
 Every case says which kernel it is for and forces or confirms it: a knob (DECODE_GROUP, DECODE_WORKGROUP_WAVES,
 EXACT_DECODER, SEQUENTIAL_INTERVALS, TILE_SAMPLES, PIXEL_MODE, set_encode_engine), a counter (exact_retry_scans must not
 rise on a speed path; charls_amd_speculation_counters[0] rises when the tile pipeline coded the scan) or a geometry that
-admits one route only (runtime.hip: wave_decode_eligible, pipeline_eligible).  Everything is compared for equality.  GPU only."""
+admits one route only (decode_launch.hip: wave_decode_eligible; encode_launch.hip: pipeline_eligible).  Everything is compared for equality.  GPU only."""
 import ctypes as C
 
 import numpy as np
@@ -187,7 +187,7 @@ def test_serial_decoder_rows_wide_samples_at_odd_addresses(torch, lib, w, h, bit
 @pytest.mark.parametrize("w,h,comps,ilv,cls,base", [(150, 3, 1, 0, "r16", 0), (33, 4, 3, 2, "p2", 0), (16, 3, 3, 1, "p2", 1), (257, 2, 3, 0, "r16p16", 0)])
 def test_wide_frames_of_one_batch_decode_at_even_and_odd_addresses(torch, lib, knobs, w, h, comps, ilv, cls, base):
     """An odd frame_pitch with an even stride: every other 16-bit frame is off the wave kernels and goes to another launch
-    than its neighbours (runtime.hip: decode_launch_key); the speed path keeps the others."""
+    than its neighbours (decode_launch.hip: decode_launch_key); the speed path keeps the others."""
     knobs.set("DECODE_GROUP", 16)
     assert decode(torch, lib, G(w, h, 16, comps, ilv), cls, base, count=9, pitch="pad", seed=w + comps) == 0
 
@@ -199,7 +199,7 @@ def test_wide_frames_of_one_batch_decode_at_even_and_odd_addresses(torch, lib, k
     (150, 10, 8, 1, 0, 0, 4, "r16", 0, False), (7, 5, 8, 3, 1, 0, 2, "p13", 1, True), (16, 7, 16, 1, 0, 0, 3, "p2", 2, False),
     (257, 3, 8, 3, 2, 0, 1, "big", 8, False), (150, 9, 8, 1, 0, 2, 4, "p1", 1, True), (16, 6, 8, 3, 0, 0, 5, "r16p16", 0, False)])
 def test_restart_interval_rows(torch, lib, knobs, sequential, w, h, bits, comps, ilv, near, lines, cls, base, tight):
-    """DRI streams of the product's encoder.  Interval-parallel: restart_intervals.hip builds a sub-scan per interval.  With
+    """DRI streams of the product's encoder.  Interval-parallel: restart_intervals_decode.hip builds a sub-scan per interval.  With
     SEQUENTIAL_INTERVALS = 1 a scan stays whole: the speed path meets the RSTm and hands exactly these scans to the exact
     decoder, which crosses the markers itself -- the retry count says so."""
     if sequential is not None:

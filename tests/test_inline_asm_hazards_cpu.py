@@ -30,7 +30,7 @@ pytestmark = pytest.mark.skipif(shutil.which(HIPCC) is None, reason="no hipcc")
 R1_STATES = 2
 R2_STATES = 4
 
-# the kernels runtime.hip launches, one of each sample width x lossless / near-lossless x lines per row, and the fast decoder
+# the kernels decode_launch.hip launches, one of each sample width x lossless / near-lossless x lines per row, and the fast decoder
 INSTANTIATIONS = """
 #include "device/scan_group_decode.hip"
 #define JLS_GROUP(S, G, NL, W, K) template __global__ void jls::decode_scans_group<S, G, NL, W, K>(const jls::ScanDesc*, jls::ScanResult*, uint32_t);

@@ -1,7 +1,7 @@
 """Shader clock, socket power and temperature at 10 Hz while the headline decoder runs with 2, 4 and 8 wavefronts per CU.
 
 DESIGN 6.2 claimed (from SQ_WAVE_CYCLES / wall time) that the chip clocks down from 2.3 to 1.8 GHz when more than two of a CU's
-four SIMDs run the group decoder, "and not every time"; the launch rule (runtime.hip: decode_group_lanes) rests on it.  This
+four SIMDs run the group decoder, "and not every time"; the launch rule (decode_launch.hip: decode_group_lanes) rests on it.  This
 tool looks at the telemetry itself: sysfs (pp_dpm_sclk, hwmon freq1_input / power1_average / power1_input / temp*_input) sampled by
 a thread during every launch, and one `rocm-smi` / `amd-smi` snapshot before and after for the record.
 
