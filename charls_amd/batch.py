@@ -116,6 +116,14 @@ def _bind(lib):
     l.charls_amd_decode_batch_device_salvage.restype = C.c_int32
     l.charls_amd_salvage_counters.argtypes = [u64p, C.c_int32]
     l.charls_amd_salvage_counters.restype = C.c_int32
+    if hasattr(l, "charls_amd_decode_batch_device_salvage_indexed"):  # (an A/B tool may load a build from before part 2h)
+        l.charls_amd_decode_batch_device_salvage_indexed.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.c_void_p, C.c_size_t, u64p,
+                                                                     C.POINTER(FrameDest), C.c_uint32, C.c_uint32,
+                                                                     C.POINTER(CodecParams), C.POINTER(capi.SalvageReport), C.c_void_p,
+                                                                     C.c_size_t, i32p, C.c_void_p]
+        l.charls_amd_decode_batch_device_salvage_indexed.restype = C.c_int32
+        l.charls_amd_salvage_index_counters.argtypes = [u64p, C.c_int32]
+        l.charls_amd_salvage_index_counters.restype = C.c_int32
     l._batch_bound = True
     return l
 
@@ -546,6 +554,61 @@ def salvage_counters(lib=None):
     n = l.charls_amd_salvage_counters(out, 4)
     assert n == 4
     return tuple(int(out[i]) for i in range(4))
+
+
+SALVAGE_PREFIX = 1  # CHARLS_AMD_SALVAGE_PREFIX
+
+
+def decode_batch_salvage_indexed(packed, offsets, sizes, outs, indexes=None, fill_value=0, *, flags=0, strides=None, capacities=None,
+                                 status_pitch=0, lib=None) -> SalvagedBatch:
+    """charls_amd_decode_batch_device_salvage_indexed: decode_batch_salvage, and for the frames it leaves failed that have a
+    seek-point index (indexes[f]: bytes, or None) the intervals between seek points that decode to the next point's state
+    (reports[f].state == 1; status 0 kept and proven, 4 kept on the index's word, 2 lost, 3 not reached); with
+    flags=SALVAGE_PREFIX a frame without a usable index keeps the rows in front of its first error (state 3; status per
+    scan: 0 whole, 5 prefix, 3 not reached).  Build the index while the stream is sound (decode_batch_and_index)."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert packed.is_cuda and packed.is_contiguous()
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    count = len(sizes)
+    assert len(offsets) >= count and len(outs) == count
+    indexes = [None] * count if indexes is None else list(indexes)
+    assert len(indexes) == count
+    index_sizes = np.array([0 if i is None else len(i) for i in indexes], dtype=np.uint64).reshape(count)
+    pitch = max([int(v) for v in index_sizes] + [1])
+    table = np.zeros((max(count, 1), pitch), dtype=np.uint8)
+    for f, i in enumerate(indexes):
+        if i is not None:
+            table[f, :len(i)] = np.frombuffer(bytes(i), dtype=np.uint8)
+    if count == 0:
+        index_sizes = np.zeros(1, dtype=np.uint64)
+    dests = _frame_dests(outs, strides, capacities)
+    params = (CodecParams * max(count, 1))()
+    reports = (capi.SalvageReport * max(count, 1))()
+    errcs = np.zeros(count, dtype=np.int32)
+    status = np.full((max(count, 1), status_pitch), 0xFF, dtype=np.uint8) if status_pitch else None
+    stream = torch.cuda.current_stream(packed.device).cuda_stream
+    rc = l.charls_amd_decode_batch_device_salvage_indexed(count, packed.data_ptr(), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                          sizes.ctypes.data_as(C.POINTER(C.c_uint64)), table.ctypes.data, pitch,
+                                                          index_sizes.ctypes.data_as(C.POINTER(C.c_uint64)), dests, int(fill_value),
+                                                          int(flags), params, reports,
+                                                          status.ctypes.data if status is not None else None, status_pitch,
+                                                          errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_decode_batch_device_salvage_indexed")
+    return SalvagedBatch(params, errcs, reports, status, last_timings(lib))
+
+
+def salvage_index_counters(lib=None):
+    """charls_amd_salvage_index_counters: (frames salvaged by index, intervals kept proven, kept on the index, lost, frames
+    salvaged by prefix, launches), process-wide since the library was loaded."""
+    l = _bind(lib or capi.load_product())
+    out = (C.c_uint64 * 6)()
+    n = l.charls_amd_salvage_index_counters(out, 6)
+    assert n == 6
+    return tuple(int(out[i]) for i in range(6))
 
 
 def encode_batch_ragged(frames, params, packed, *, alignment=1, strides=None, max_stream_bytes=None, capacity=None, lib=None) -> PackedBatch:

@@ -46,6 +46,7 @@ SOURCES = [
     "host/batch_ragged.cpp",
     "host/batch_budget.cpp",
     "host/batch_salvage.cpp",
+    "host/batch_salvage_index.cpp",
     "host/multi_device.cpp",
 ]
 

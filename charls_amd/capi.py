@@ -382,6 +382,33 @@ class CharLSLibrary:
         finally:
             L.charls_jpegls_decoder_destroy(dec)
 
+    def decode_salvage_indexed(self, data, index=None, fill_value=0, flags=0, stride=0, status_capacity=None):
+        """charls_amd_jpegls_decoder_decode_to_buffer_salvage_indexed (product library only), after set_index where `index`
+        is given: (Header, raw destination bytes, SalvageReport, status bytes, errc).  With report.state 1 or 3 the
+        destination holds the salvaged frame."""
+        L = self._index_fns()
+        fn = L.charls_amd_jpegls_decoder_decode_to_buffer_salvage_indexed
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SalvageReport), C.c_void_p,
+                       C.c_size_t]
+        fn.restype = C.c_int32
+        dec, keep = self._open(data)
+        try:
+            hdr = self._header(dec)
+            if index is not None:
+                self.set_index(dec, index)
+            sz = C.c_size_t()
+            self._check(L.charls_jpegls_decoder_get_destination_size(dec, stride, C.byref(sz)), "get_dest_size")
+            out = np.zeros(sz.value, dtype=np.uint8)
+            if status_capacity is None:
+                status_capacity = hdr.component_count * hdr.height
+            status = np.full(max(status_capacity, 1), 0xFF, dtype=np.uint8)
+            report = SalvageReport()
+            rc = fn(dec, out.ctypes.data, out.nbytes, stride, fill_value, flags, C.byref(report), status.ctypes.data, status_capacity)
+            del keep
+            return hdr, out, report, status[:status_capacity], rc
+        finally:
+            L.charls_jpegls_decoder_destroy(dec)
+
     def decode_rows(self, data, first_row, row_count, index=None, stride=0):
         """Rows [first_row, first_row + row_count) in decode_to_buffer's layout for a frame of row_count rows (planar
         frames: one band per component).  With `index`, from the seek point at or before first_row."""

@@ -427,6 +427,29 @@ void launch_decode_salvage(const ScanDesc& proto, const ScanDesc* d_descs, uint3
         outputs.segment_ends[i] = segments[i].end;
 }
 
+static_assert(kSalvageByIndex == salvage::kByIndex && kSalvageByPrefix == salvage::kByPrefix &&
+              kSalvageEndsInNextPoint == salvage::kEndsInNextPoint);
+
+void launch_salvage_fill(const ScanDesc& proto, const ScanDesc* d_parents, uint32_t count, uint32_t intervals,
+                         const ScanResult* d_results, const uint64_t* d_expect, uint8_t* d_status, uint32_t fill_value, uint32_t rule,
+                         hipStream_t stream)
+{
+    if (count == 0 || intervals == 0)
+        return;
+    if ((rule != kSalvageByIndex && rule != kSalvageByPrefix) || intervals > 0x7FFFFFFFu)
+        raise(CHARLS_JPEGLS_ERRC_INVALID_OPERATION);
+    const uint64_t row_bytes = static_cast<uint64_t>(proto.width) * (proto.interleave_mode == 0 ? 1 : proto.components) *
+                               (proto.bits_per_sample > 8 ? 2 : 1);
+    for (uint32_t first = 0; first < count; first += 65535u) // (a grid has at most 65535 rows)
+    {
+        const size_t at = static_cast<size_t>(first) * intervals;
+        hipLaunchKernelGGL(salvage::judge_and_fill, dim3(intervals, std::min(count - first, 65535u)), dim3(salvage::kFillThreads), 0, stream,
+                           d_parents + first, intervals, d_results + at, d_expect + at, d_status + at, fill_value,
+                           (proto.bits_per_sample > 8 ? salvage::kWideSamples : 0u) | rule, row_bytes);
+        hip_check(hipGetLastError());
+    }
+}
+
 void launch_decode(const ScanDesc& proto, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
                    hipStream_t stream)
 {

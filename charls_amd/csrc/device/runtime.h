@@ -127,6 +127,19 @@ struct SalvageOutputs
 void launch_decode_salvage(const ScanDesc& proto, const ScanDesc* d_descs, uint32_t count, const SalvageOutputs& outputs,
                            hipStream_t stream);
 uint64_t salvage_kernel_launches() noexcept; // launches of the three salvage kernels since the library was loaded
+// Salvage through the seek-point index (charls_amd.h part 2h; host/batch_salvage_index.cpp): judge_and_fill over the results
+// of a launch of decode_scans_wave_resume.  `count` parents of proto's row length, `intervals` results, expected values and
+// status bytes each (scan-major, DEVICE); a parent's restart_interval is the lines per interval.  The host sets status 0 for
+// the intervals it launched and 3 for the others, and finds the verdicts there afterwards.
+//   kSalvageByIndex   kept: no error, and the end state was compared and equals the next point (expect = kSalvageEndsInNextPoint)
+//                     or the scan ended with `expect` bytes consumed; every other interval's rows are filled
+//   kSalvageByPrefix  one interval per scan (seek::kResumePrefix): an error makes it 5, and its rows from the row the result
+//                     names are filled
+constexpr uint32_t kSalvageByIndex = 2u, kSalvageByPrefix = 4u;
+constexpr uint64_t kSalvageEndsInNextPoint = ~uint64_t{0};
+void launch_salvage_fill(const ScanDesc& proto, const ScanDesc* d_parents, uint32_t count, uint32_t intervals,
+                         const ScanResult* d_results, const uint64_t* d_expect, uint8_t* d_status, uint32_t fill_value, uint32_t rule,
+                         hipStream_t stream);
 
 // Encoder dispatch.  All `count` scans share the geometry / coding mode of `proto` (HOST copy of one of them; its
 // stream_capacity is an upper bound of every scan's capacity).  Lossless single-component scans go through the

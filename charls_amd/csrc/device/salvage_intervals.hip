@@ -18,6 +18,9 @@
 //   judge_and_fill        grid (interval, scan): an interval is KEPT when its scan ended kOk, with no undecided flag, having
 //                         consumed exactly its piece (check_intervals' criterion); the rows of every other interval are filled
 //                         with the caller's sample value -- after the decoders, which may have written part of them.
+//                         It also judges and fills for the salvage through the seek-point index (charls_amd.h part 2h;
+//                         host/batch_salvage_index.cpp), where the intervals are work items of decode_scans_wave_resume:
+//                         bits of its `wide` argument choose that criterion (kByIndex, kByPrefix).
 //
 // Memory rules.  The marker search reads whole aligned 16-byte granules that hold at least one byte of the scan's stream
 // (find_restart_markers' rule).  judge_and_fill writes the rows of lost intervals and nothing else: bytes [0, row_bytes) of
@@ -42,7 +45,19 @@ enum : uint8_t
     kUnclaimed = 1,  // no piece claimed the interval
     kNotExact = 2,   // its piece did not decode to its exact length
     kNotReached = 3, // the scan was not reached (a parent without a stream)
+    kOnTheIndex = 4, // part 2h, set by the host: kept, from a seek point behind a lost interval
+    kPrefix = 5,     // part 2h, prefix mode: the scan's rows before its error stay, the rest is filled
 };
+
+// judge_and_fill's `wide`: bit 0 says that samples have 16 bits; the others choose the criterion (none: part 2g's).
+enum : uint32_t
+{
+    kWideSamples = 1u,
+    kByIndex = 2u,  // intervals between seek points (charls_amd.h part 2h): expect[at] = kEndsInNextPoint, or the bytes the
+                    // scan's last interval must have consumed when it ended the scan
+    kByPrefix = 4u, // one "interval" per scan, decoded from the top: lost rows begin at the row the result names
+};
+constexpr uint64_t kEndsInNextPoint = ~uint64_t{0};
 
 // 16 bytes as one load or store through an address-space pointer (a class type cannot be copied through one).
 typedef uint32_t Words4 __attribute__((vector_size(16)));
@@ -244,7 +259,9 @@ __global__ void __launch_bounds__(64) plan_salvage(const ScanDesc* __restrict__ 
 constexpr uint32_t kFillThreads = 256;
 
 // grid (intervals, scans) x 256.  status holds plan_salvage's provisional bytes and gets the verdicts.  `fill`: the sample
-// value for lost rows; `wide`: 16-bit samples; row_bytes: the bytes of a row that are pixels (the same for every scan).
+// value for lost rows; `wide`: 16-bit samples (bit 0) and the criterion (kByIndex, kByPrefix: the intervals are work items
+// of decode_scans_wave_resume, `status` and `expect` come from the host, the interval length is the parents'
+// restart_interval as ever); row_bytes: the bytes of a row that are pixels (the same for every scan).
 __global__ void __launch_bounds__(256) judge_and_fill(const ScanDesc* __restrict__ parents, uint32_t intervals,
                                                       const ScanResult* __restrict__ sub_results, const uint64_t* __restrict__ expect,
                                                       uint8_t* __restrict__ status, uint32_t fill, uint32_t wide, uint64_t row_bytes)
@@ -252,10 +269,27 @@ __global__ void __launch_bounds__(256) judge_and_fill(const ScanDesc* __restrict
     const uint32_t j = blockIdx.x, s = blockIdx.y;
     const size_t at = (size_t)s * intervals + j;
     uint8_t verdict = global_ptr(status)[at]; // (every thread reads it before thread 0 may write it: the barrier below)
+    uint64_t whole_rows = 0;                  // rows at the interval's top that stay although it is not kept (kByPrefix)
     if (verdict == kKept)
     {
         const ScanResult r = sub_results[at];
-        if (r.errc != kOk || (r.flags & kUndecidedFlags) != 0 || r.bytes != global_ptr(expect)[at])
+        const uint64_t want = global_ptr(expect)[at];
+        if ((wide & kByPrefix) != 0)
+        { // a scan from the top on decode_scans_wave_resume, seek::kResumePrefix: an error names the row it came in
+            if (r.errc != kOk)
+            {
+                verdict = kPrefix;
+                whole_rows = r.bytes;
+            }
+        }
+        else if ((wide & kByIndex) != 0)
+        { // an interval of decode_scans_wave_resume: it ends in the next point's state, or ends the scan where the index says
+            // (flag bit 2 is seek::kSeekChecked here, not an undecided speed path)
+            const bool holds = want == kEndsInNextPoint ? (r.flags & (2u | 4u)) == 4u : r.bytes == want;
+            if (r.errc != kOk || !holds)
+                verdict = kNotExact;
+        }
+        else if (r.errc != kOk || (r.flags & kUndecidedFlags) != 0 || r.bytes != want)
             verdict = kNotExact;
     }
     __syncthreads();
@@ -266,11 +300,11 @@ __global__ void __launch_bounds__(256) judge_and_fill(const ScanDesc* __restrict
 
     const ScanDesc d = parents[s];
     const uint32_t lines = d.restart_interval;
-    const uint64_t first = (uint64_t)j * lines;
-    if (first >= d.height)
+    const uint64_t first = (uint64_t)j * lines + whole_rows;
+    if (first >= d.height || whole_rows >= lines)
         return;
-    const uint32_t rows = (uint32_t)(d.height - first < lines ? d.height - first : lines);
-    const uint32_t lo = fill & 0xFFu, hi = wide ? (fill >> 8) & 0xFFu : lo;
+    const uint32_t rows = (uint32_t)(d.height - first < lines - whole_rows ? d.height - first : lines - whole_rows);
+    const uint32_t lo = fill & 0xFFu, hi = (wide & kWideSamples) != 0 ? (fill >> 8) & 0xFFu : lo;
     const uint64_t pair = (uint64_t)lo | ((uint64_t)hi << 8);
     const uint64_t even = pair * 0x0001000100010001ull;      // a granule that starts on an even byte of the row
     const uint64_t odd = (even >> 8) | ((uint64_t)lo << 56); // on an odd one

@@ -5,7 +5,8 @@
 //    (0 < y < height), writes seek point i (layout: seek_decode.h).
 //  * decode_scans_wave_resume decodes rows [first_row, end_row) of a scan from the initial state (first_row = 0) or from a
 //    seek point, stores the rows asked for, and then compares its end state with the next seek point, ends the scan
-//    (end_scan, bytes consumed), or just stops (a band of rows).
+//    (end_scan, bytes consumed), or just stops (a band of rows).  In prefix mode (salvage through the index, charls_amd.h
+//    part 2h) it ends the scan as well, and where it stops on an error it reports the rows it completed instead.
 // Both run the line loop of scan_wave_decode.hip unchanged; what is new is the state going out to and coming in from
 // global memory.  Positions are stored relative to the scan's first entropy-coded byte: the device copy of a stream has a
 // different 16-byte misalignment from one call to the next, and the LDS ring is only a cache of the bytes.
@@ -223,7 +224,8 @@ __global__ void __launch_bounds__(64) decode_scans_wave_resume(const ScanDesc* _
         __syncthreads();
     }
 
-    for (uint32_t y = w.first_row; y < w.end_row && br.err == kOk; ++y)
+    uint32_t y = w.first_row; // (behind the loop: the rows that were completed, first_row + their count)
+    for (; y < w.end_row && br.err == kOk; ++y)
     {
         if (NC > 1)
             decode_line<S, NC>(t, m, br, line, ps, d.width, corner, run_index[0], lane);
@@ -237,7 +239,8 @@ __global__ void __launch_bounds__(64) decode_scans_wave_resume(const ScanDesc* _
         JLS_LOCKSTEP();
     }
     uint32_t flags = 1;
-    if (br.err == kOk && w.mode == seek::kResumeEnd)
+    const bool ends_scan = w.mode == seek::kResumeEnd || w.mode == seek::kResumePrefix;
+    if (br.err == kOk && ends_scan)
         br.end_scan();
     else if (br.err == kOk && w.mode == seek::kResumeCompare)
     {
@@ -251,7 +254,9 @@ __global__ void __launch_bounds__(64) decode_scans_wave_resume(const ScanDesc* _
         ScanResult r;
         r.errc = br.err;
         r.flags = flags;
-        r.bytes = br.err == kOk && w.mode == seek::kResumeEnd ? br.consumed_bytes() : 0;
+        r.bytes = br.err == kOk && ends_scan ? br.consumed_bytes() : 0;
+        if (br.err != kOk && w.mode == seek::kResumePrefix)
+            r.bytes = y; // the rows before the error are whole, and stored where the item stores rows
         results[blockIdx.x] = r;
     }
 }

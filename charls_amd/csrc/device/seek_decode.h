@@ -57,6 +57,8 @@ enum : uint32_t
     kResumeBand = 0,    // decode, store the rows asked for, stop
     kResumeCompare = 1, // ... then compare the end state with the point at `to_point`
     kResumeEnd = 2,     // ... then end the scan (end_scan) and report the bytes consumed, as decode_scans_wave does
+    kResumePrefix = 3,  // as kResumeEnd; an item that stops on an error reports in ScanResult.bytes the row behind the
+                        // last one it completed (first_row where there is none): rows [first_row, bytes) are whole
 };
 // ScanResult.flags of a resumed interval: bit 0 as decode_scans_wave sets it, and the outcome of a comparison.
 enum : uint32_t

@@ -42,6 +42,17 @@ void decode_batch_salvage(uint32_t frame_count, const void* d_packed, const uint
                           charls_amd_salvage_report* reports, uint8_t* interval_status, size_t status_pitch_bytes,
                           charls_jpegls_errc* errcs, void* hip_stream);
 
+// charls_amd_decode_batch_device_salvage_indexed (batch_salvage_index.cpp): decode_batch_salvage, then the index and prefix
+// modes of part 2h for the frames it leaves in state 2.  Frame f's index is *parsed_indexes[f] where that array and the
+// entry are there (the part-1 call hands over the handle's), else the index_sizes[f] bytes at indexes + f * index_pitch_bytes
+// (HOST; index_sizes may be nullptr: no indexes).  frame_count >= 1, flags and pointers checked by the caller.
+struct SeekIndex;
+void decode_batch_salvage_indexed(uint32_t frame_count, const void* d_packed, const uint64_t* offsets, const uint64_t* sizes,
+                                  const SeekIndex* const* parsed_indexes, const void* indexes, size_t index_pitch_bytes,
+                                  const uint64_t* index_sizes, const charls_amd_frame_dest* dests, uint32_t fill_value, uint32_t flags,
+                                  charls_amd_codec_params* params_out, charls_amd_salvage_report* reports, uint8_t* interval_status,
+                                  size_t status_pitch_bytes, charls_jpegls_errc* errcs, void* hip_stream);
+
 // The batch encoder behind charls_amd_encode_batch_device with every frame's pixels named by a pointer of its own
 // (d_pixels: HOST array of frame_count DEVICE pointers; the slot call passes d_frames + i * frame_pitch_bytes): frame i's
 // .jls goes to d_streams + i * stream_pitch_bytes.  `frame_bytes` is what every frame offers from its pointer on (the slot

@@ -245,8 +245,9 @@ struct charls_jpegls_decoder
     }
 
     // decode_to_buffer, and where it fails the salvage round of part 2g on this one frame.  Raises what decode raises.
+    // `by_index`: part 2h's call -- the handle's index (set_index) and `flags` serve the frame that part 2g leaves failed.
     void decode_salvaging(void* destination, size_t size, size_t stride_arg, uint32_t fill_value, charls_amd_salvage_report& report,
-                          uint8_t* interval_status, size_t status_capacity)
+                          uint8_t* interval_status, size_t status_capacity, bool by_index = false, uint32_t flags = 0)
     {
         check_buffer(destination, size);
         check_operation(state == State::header_read);
@@ -260,22 +261,23 @@ struct charls_jpegls_decoder
         {
             try
             {
-                salvage(header, destination, size, stride_arg, fill_value, report, interval_status, status_capacity);
+                salvage(header, destination, size, stride_arg, fill_value, report, interval_status, status_capacity, by_index, flags);
             }
             catch (const error&)
             { // (nothing salvaged; the call reports what decode_to_buffer reports)
                 report.state = 0;
             }
-            if (report.state != 1) // (whatever a second decode made of the frame: the first one failed, nothing is handed out)
-                report = charls_amd_salvage_report{2, 0, 0, 0, UINT32_MAX, 0};
+            if (report.state != 1 && report.state != 3) // (whatever a second decode made of the frame: the first one failed, nothing is handed out)
+                report = charls_amd_salvage_report{2, 0, 0, 0, UINT32_MAX, report.state == 2 ? report.reserved & 2u : 0u};
             throw;
         }
     }
 
-    // The whole source goes to the handle's device buffers, the batch routine (batch_salvage.cpp) runs on that one frame, and
-    // the rows of a salvaged frame come back.  `header`: the reader as it stood behind the first scan's header.
+    // The whole source goes to the handle's device buffers, the batch routine (batch_salvage.cpp, batch_salvage_index.cpp) runs
+    // on that one frame, and the rows of a salvaged frame come back.  `header`: the reader as it stood behind the first scan's
+    // header.
     void salvage(const StreamReader& header, void* destination, size_t size, size_t stride_arg, uint32_t fill_value,
-                 charls_amd_salvage_report& report, uint8_t* interval_status, size_t status_capacity)
+                 charls_amd_salvage_report& report, uint8_t* interval_status, size_t status_capacity, bool by_index, uint32_t flags)
     {
         const auto [row, stride] = row_and_stride(header, stride_arg);
         const size_t rows = static_cast<size_t>(header.frame_info().height) * scans_of_frame(header);
@@ -285,9 +287,17 @@ struct charls_jpegls_decoder
         const uint64_t offset = 0, bytes = source_size;
         const charls_amd_frame_dest dest{staged.d_pixels, row * rows, 0, 0}; // (device rows are packed)
         charls_jpegls_errc errc{};
-        decode_batch_salvage(1, staged.d_stream, &offset, &bytes, &dest, fill_value, nullptr, &report, interval_status,
-                             interval_status != nullptr ? std::max<size_t>(status_capacity, 1) : 0, &errc, staged.stream);
-        if (report.state == 1)
+        const size_t status_pitch = interval_status != nullptr ? std::max<size_t>(status_capacity, 1) : 0;
+        if (by_index)
+        {
+            const SeekIndex* given = has_index ? &index : nullptr;
+            decode_batch_salvage_indexed(1, staged.d_stream, &offset, &bytes, &given, nullptr, 0, nullptr, &dest, fill_value, flags, nullptr,
+                                         &report, interval_status, status_pitch, &errc, staged.stream);
+        }
+        else
+            decode_batch_salvage(1, staged.d_stream, &offset, &bytes, &dest, fill_value, nullptr, &report, interval_status, status_pitch, &errc,
+                                 staged.stream);
+        if (report.state == 1 || report.state == 3)
             engine.fetch_staged_rows(static_cast<uint8_t*>(destination), stride, row, rows);
     }
 
@@ -444,6 +454,21 @@ charls_jpegls_errc charls_amd_jpegls_decoder_decode_to_buffer_salvage(charls_jpe
     check_buffer(interval_status, status_capacity);
     d->index_mode = IndexMode::none; // (launches on its own, from the top)
     d->decode_salvaging(destination, size, stride, fill_value, *report, interval_status, status_capacity);
+    JLS_THUNK_END
+}
+
+charls_jpegls_errc charls_amd_jpegls_decoder_decode_to_buffer_salvage_indexed(charls_jpegls_decoder* d, void* destination, size_t size,
+                                                                              uint32_t stride, uint32_t fill_value, uint32_t flags,
+                                                                              charls_amd_salvage_report* report, uint8_t* interval_status,
+                                                                              size_t status_capacity)
+{
+    JLS_THUNK_BEGIN
+    check_pointer(d);
+    check_pointer(report);
+    check_argument((flags & ~static_cast<uint32_t>(CHARLS_AMD_SALVAGE_PREFIX)) == 0);
+    check_buffer(interval_status, status_capacity);
+    d->index_mode = IndexMode::none; // (round 1 launches on its own, from the top; the index serves the frame it fails on)
+    d->decode_salvaging(destination, size, stride, fill_value, *report, interval_status, status_capacity, true, flags);
     JLS_THUNK_END
 }
 

@@ -729,16 +729,16 @@ CHARLS_AMD_API int32_t charls_amd_measure_counters(uint64_t* out, int32_t capaci
  *   round took in ms by the host's clock (each of its launches ends in a synchronise).
  * salvage_counters: out[0] frames salvaged, out[1] intervals kept, out[2] intervals lost, out[3] launches of the salvage
  *   kernels; process-wide since load; returns the number of values written (4 at most).
- * Not done: streams without restart intervals, partial intervals, the slot, indexed and multi-device calls.
+ * Not done: partial intervals, the slot and multi-device calls.  Streams without restart intervals: part 2h.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct charls_amd_salvage_report
 {
-    uint32_t state;          /* 0 decoded whole; 1 salvaged; 2 failed and nothing salvaged */
+    uint32_t state;          /* 0 decoded whole; 1 salvaged; 2 failed and nothing salvaged; 3 (part 2h) the rows before the error */
     uint32_t intervals;      /* restart intervals of the frame, summed over its scans (state 1; else 0) */
     uint32_t intervals_lost;
     uint32_t rows_lost;      /* rows filled, summed over scans (a planar frame counts each plane's rows) */
     uint32_t first_lost_row; /* lowest row of the frame that holds fill in any scan; UINT32_MAX: none */
-    uint32_t reserved;       /* written as 0 (1: status_pitch_bytes was too small for this frame) */
+    uint32_t reserved;       /* written as 0 (bit 0: status_pitch_bytes was too small for this frame; bit 1, part 2h: its index was not usable) */
 } charls_amd_salvage_report;
 
 CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_device_salvage(
@@ -749,6 +749,77 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_jpegls_decoder_decode_to_buffer_sal
     charls_jpegls_decoder* decoder, void* destination, size_t size, uint32_t stride, uint32_t fill_value,
     charls_amd_salvage_report* report, uint8_t* interval_status, size_t status_capacity);
 CHARLS_AMD_API int32_t charls_amd_salvage_counters(uint64_t* out, int32_t capacity);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Part 2h -- SALVAGE decode through the SEEK-POINT INDEX: streams without restart markers.  The reference's encoder never
+ * writes restart markers, so part 2g helps none of the files it wrote.  A seek-point index (part 1 extension, part 2c) that
+ * was built while the stream was sound holds the complete decoder state every K lines; it confines damage the same way.
+ * Argument for argument the calls are part 2g's, with the indexes of part 2c (HOST; index_sizes[f] == 0: frame f has none;
+ * `indexes` may be NULL when every size is 0) and `flags`: bit 0 CHARLS_AMD_SALVAGE_PREFIX, any other bit is
+ * invalid_argument for the call.  The whole-call checks are part 2g's plus index_sizes == NULL, all made before a device is
+ * asked for; frame_count == 0 is success.
+ *
+ * Round 1 is charls_amd_decode_batch_device_ragged, unchanged, exactly as in part 2g (state 0; a batch without failed frames
+ *   launches nothing else; errcs[f] stays round 1's for salvaged frames, but for a fill_value above MAXVAL).
+ * Round 2 takes a failed frame whose header was read, whose first scan was located, and which passed its stride and capacity
+ *   checks:
+ * 1. A frame part 2g salvages is salvaged exactly as there: the same report and status bytes, state 1.
+ * 2. INDEX MODE (state 1): index_sizes[f] != 0, the index passes set_index's checks (format, the frame it names, every
+ *   field's range) and has seek points for every scan, the scans are ones the seek kernels take (part 2c), the height does
+ *   not come from DNL, and the rows of 16-bit frames lie at even addresses.  The segment hash is NOT consulted: it cannot
+ *   match a damaged segment.  With K the index's lines and N = ceil(height / K), interval i of scan c covers rows
+ *   [iK, min(height, (i+1)K)).  It starts from the scan's initial state at the segment start (i = 0) or from point i, and is
+ *   KEPT if and only if it decodes without error and, for i < N-1, ends in exactly the state of point i+1 (the comparison
+ *   part 1's chain check makes: contexts, run state, previous line, reader position and cache); for i = N-1, the scan ends
+ *   and the bytes consumed equal the segment length the index names.  Every other interval is LOST: all of its rows get
+ *   fill_value after the decoders have run -- rows decoded before the error too; nothing unverified is kept in this mode.
+ *   An interval whose point puts the reader beyond the source bytes that are left is not started (status 3).  Scan c+1 of
+ *   a planar frame is looked for at scan c's segment start plus the length the index names for it -- a damaged scan does not
+ *   hide the ones behind it, as it does in part 2g; with no valid SOS of a scan of the same kind there, the intervals of that
+ *   scan and of the scans behind it are not reached.
+ *   Status bytes, one per (scan, interval), scan-major:
+ *     0  kept, and so is every interval above it in the scan: exact whatever the index holds, by induction from the true
+ *        initial state
+ *     4  kept on the index's word: its start state came from a point that the chain no longer proves
+ *     2  did not decode to the next point's state
+ *     3  not reached
+ *   STATUS 4 IS AS GOOD AS THE INDEX.  Set only an index that was built from this very stream while it was sound.  A wrong
+ *   index loses intervals.  A forged one can give wrong pixels in status-4 intervals, but never a read or a write out of
+ *   bounds.  An index that is refused or lacks points counts as absent; reports[f].reserved bit 1 (value 2) says so.
+ * 3. PREFIX MODE (state 3): only with CHARLS_AMD_SALVAGE_PREFIX and no usable index, under the same conditions on scans and
+ *   rows.  The frame is decoded from the top on the exact decoder.  Scan c fails after r complete rows: scans before c are
+ *   whole, rows [0, r) of scan c are what the decoder produced, rows [r, height) of scan c and every later scan get
+ *   fill_value.  One status byte per scan: 0 whole, 5 prefix, 3 not reached; `intervals` counts scans, intervals_lost those
+ *   that are not whole, first_lost_row the lowest row that holds fill in any scan.  This is what the reference leaves in a
+ *   caller's buffer.  It is right for truncated files and UNVERIFIED after a bit error: on a 70x40 8-bit frame of 1275
+ *   bytes with 4 bytes zeroed in the middle the reference's decoder writes 38 rows before it raises invalid_data and only
+ *   the first 19 equal the sound image (12-bit: 35 written, 19 right; 35x24 RGB line- and sample-interleaved: 22-23 written,
+ *   11 right; cut in the middle and closed with FF D9: 19 written, all 19 right).  Rows behind a bit error are mostly
+ *   garbage that nobody can tell from pixels; the index tells them apart and gives back what lies below the damage.
+ * 4. Every other failed frame gets state 2, as in part 2g.
+ * In every mode nothing is written outside the rows of a frame's own destination, and one frame's damage never changes
+ *   another frame's result.
+ * charls_amd_jpegls_decoder_decode_to_buffer_salvage_indexed: the same for one stream in host memory, after read_header and,
+ *   optionally, set_index.  Returns what decode_to_buffer returns; with state 1 or 3 `destination` holds the salvaged frame.
+ * charls_amd_last_timings after the batch call: [2] as in part 2g, covering everything behind round 1; [3] the launches of
+ *   this part by device events, ms.
+ * salvage_index_counters: out[0] frames salvaged by index, out[1] intervals kept proven (0), out[2] kept on the index (4),
+ *   out[3] lost (2, 3), out[4] frames salvaged by prefix, out[5] kernel launches of this part (one of the resume kernel and
+ *   one of the fill kernel per group of scans that share sample width, interleaving, geometry and K); process-wide since
+ *   load; returns the number of values written (6 at most).
+ * Not done: partial intervals in index mode, the slot and multi-device calls, building an index from a damaged stream.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define CHARLS_AMD_SALVAGE_PREFIX 1u
+
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_device_salvage_indexed(
+    uint32_t frame_count, const void* d_packed, const uint64_t* offsets, const uint64_t* sizes, const void* indexes,
+    size_t index_pitch_bytes, const uint64_t* index_sizes, const charls_amd_frame_dest* dests, uint32_t fill_value, uint32_t flags,
+    charls_amd_codec_params* params_out, charls_amd_salvage_report* reports, uint8_t* interval_status, size_t status_pitch_bytes,
+    charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_jpegls_decoder_decode_to_buffer_salvage_indexed(
+    charls_jpegls_decoder* decoder, void* destination, size_t size, uint32_t stride, uint32_t fill_value, uint32_t flags,
+    charls_amd_salvage_report* report, uint8_t* interval_status, size_t status_capacity);
+CHARLS_AMD_API int32_t charls_amd_salvage_index_counters(uint64_t* out, int32_t capacity);
 
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */
