@@ -124,6 +124,29 @@ def _bind(lib):
         l.charls_amd_decode_batch_device_salvage_indexed.restype = C.c_int32
         l.charls_amd_salvage_index_counters.argtypes = [u64p, C.c_int32]
         l.charls_amd_salvage_index_counters.restype = C.c_int32
+    if hasattr(l, "charls_amd_encode_batch_host_ragged"):  # (part 2i; an A/B tool may load a build from before it)
+        l.charls_amd_host_alloc.argtypes = [C.c_size_t]
+        l.charls_amd_host_alloc.restype = C.c_void_p
+        l.charls_amd_host_free.argtypes = [C.c_void_p]
+        l.charls_amd_host_free.restype = None
+        l.charls_amd_host_register.argtypes = [C.c_void_p, C.c_size_t]
+        l.charls_amd_host_register.restype = C.c_int32
+        l.charls_amd_host_unregister.argtypes = [C.c_void_p]
+        l.charls_amd_host_unregister.restype = C.c_int32
+        l.charls_amd_probe_batch_host_packed.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.POINTER(CodecParams), u64p, i32p]
+        l.charls_amd_probe_batch_host_packed.restype = C.c_int32
+        l.charls_amd_encode_batch_host_ragged.argtypes = [C.c_uint32, C.POINTER(FrameSource), C.c_void_p, C.c_size_t, C.c_uint32, u64p, u64p, i32p]
+        l.charls_amd_encode_batch_host_ragged.restype = C.c_int32
+        l.charls_amd_decode_batch_host_ragged.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.POINTER(FrameDest), C.POINTER(CodecParams), i32p]
+        l.charls_amd_decode_batch_host_ragged.restype = C.c_int32
+        l.charls_amd_encode_batch_host.argtypes = [C.POINTER(CodecParams), C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                   C.c_uint32, C.c_size_t, u64p, u64p, i32p]
+        l.charls_amd_encode_batch_host.restype = C.c_int32
+        l.charls_amd_decode_batch_host.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                   C.POINTER(CodecParams), i32p]
+        l.charls_amd_decode_batch_host.restype = C.c_int32
+        l.charls_amd_host_counters.argtypes = [u64p, C.c_int32]
+        l.charls_amd_host_counters.restype = C.c_int32
     l._batch_bound = True
     return l
 
@@ -640,6 +663,220 @@ def encode_batch_ragged(frames, params, packed, *, alignment=1, strides=None, ma
     if rc != 0:
         raise capi.JpegLSError(rc, "charls_amd_encode_batch_device_ragged")
     return PackedBatch(packed, offsets, sizes, errcs)
+
+
+# ---- host memory (charls_amd.h part 2i): numpy arrays or CPU torch tensors in, host bytes out, the copies inside the call ---
+
+class _PinnedBlock:
+    """Memory of charls_amd_host_alloc, freed when the last array that looks at it is gone."""
+
+    def __init__(self, l, nbytes):
+        self._l, self.address = l, l.charls_amd_host_alloc(nbytes)
+        if not self.address:
+            raise MemoryError("charls_amd_host_alloc: no usable device, or no memory")
+        self.__array_interface__ = {"data": (self.address, False), "shape": (nbytes,), "typestr": "|u1", "version": 3}
+
+    def __del__(self):
+        if getattr(self, "address", None):
+            self._l.charls_amd_host_free(self.address)
+            self.address = None
+
+
+def host_alloc(nbytes, *, lib=None) -> np.ndarray:
+    """charls_amd_host_alloc: a uint8 array of pinned host memory (view it as another dtype, slice it, reshape it)."""
+    l = _bind(lib or capi.load_product())
+    return np.asarray(_PinnedBlock(l, int(nbytes)))
+
+
+def _host(x):
+    """(address, shape, strides in bytes, bytes per element) of a numpy array or a CPU torch tensor."""
+    if isinstance(x, np.ndarray):
+        return x.ctypes.data, x.shape, x.strides, x.itemsize
+    assert not x.is_cuda, "host memory: a numpy array or a CPU tensor"
+    return x.data_ptr(), tuple(x.shape), tuple(s * x.element_size() for s in x.stride()), x.element_size()
+
+
+def _host_contiguous(x):
+    address, shape, strides, item = _host(x)
+    expect = item
+    for n, s in zip(reversed(shape), reversed(strides)):
+        assert n == 1 or s == expect, "host memory that is one contiguous block"
+        expect *= n
+    return address, expect  # (address, bytes)
+
+
+def _host_rows(x, planar):
+    """(address, stride argument, extent in bytes) of one frame: a contiguous array (stride 0), or a view with padded rows --
+    (H, W) and (H, W, C) views with contiguous rows, (C, H, W) views whose planes follow each other."""
+    address, shape, strides, item = _host(x)
+    if len(shape) == 3 and planar:
+        assert strides[2] == item and strides[0] == strides[1] * shape[1], "a planar view's planes must follow each other"
+        row, rows, stride = shape[2] * item, shape[0] * shape[1], strides[1]
+    elif len(shape) == 3:
+        assert strides[2] == item and strides[1] == shape[2] * item, "a view's rows must be contiguous"
+        row, rows, stride = shape[1] * shape[2] * item, shape[0], strides[0]
+    else:
+        assert len(shape) == 2 and strides[1] == item, "a view's rows must be contiguous"
+        row, rows, stride = shape[1] * item, shape[0], strides[0]
+    return address, (0 if stride == row else stride), (stride * (rows - 1) + row if rows else 0)
+
+
+def host_register(x, *, lib=None):
+    """charls_amd_host_register: pins the memory of a contiguous array the caller owns (undo with host_unregister)."""
+    l = _bind(lib or capi.load_product())
+    address, nbytes = _host_contiguous(x)
+    rc = l.charls_amd_host_register(address, nbytes)
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_host_register")
+
+
+def host_unregister(x, *, lib=None):
+    l = _bind(lib or capi.load_product())
+    rc = l.charls_amd_host_unregister(_host_contiguous(x)[0])
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_host_unregister")
+
+
+def host_counters(lib=None):
+    """charls_amd_host_counters: (calls, windows, bytes up, bytes down, pageable bytes staged, device bytes held, pinned bytes held)."""
+    l = _bind(lib or capi.load_product())
+    out = (C.c_uint64 * 7)()
+    n = l.charls_amd_host_counters(out, 7)
+    assert n == 7
+    return tuple(int(out[i]) for i in range(7))
+
+
+def _tables(offsets, sizes):
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    assert len(offsets) >= len(sizes)
+    return offsets, sizes, len(sizes)
+
+
+def probe_host(packed, offsets, sizes, *, lib=None):
+    """charls_amd_probe_batch_host_packed: probe_packed on host bytes; needs no GPU.  Returns (params, frame_bytes, errcs)."""
+    l = _bind(lib or capi.load_product())
+    offsets, sizes, count = _tables(offsets, sizes)
+    params = (CodecParams * max(count, 1))()
+    frame_bytes = np.zeros(count, dtype=np.uint64)
+    errcs = np.zeros(count, dtype=np.int32)
+    u64p = C.POINTER(C.c_uint64)
+    rc = l.charls_amd_probe_batch_host_packed(count, _host_contiguous(packed)[0], offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p), params,
+                                              frame_bytes.ctypes.data_as(u64p), errcs.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_probe_batch_host_packed")
+    return params, frame_bytes, errcs
+
+
+def encode_batch_host_ragged(frames, params, packed, *, alignment=1, strides=None, max_stream_bytes=None, capacity=None, lib=None) -> PackedBatch:
+    """charls_amd_encode_batch_host_ragged: encode_batch_ragged with frames[f] and `packed` in HOST memory -- numpy arrays or
+    CPU tensors, pinned or pageable, views with padded rows (their row stride is read from the view)."""
+    l = _bind(lib or capi.load_product())
+    count = len(frames)
+    if isinstance(params, CodecParams):
+        params = [params] * count
+    assert len(params) == count
+    sources = (FrameSource * max(count, 1))()
+    for f, x in enumerate(frames):
+        if strides is not None:  # (the caller says where the rows are: x may be any view that starts at the first row)
+            address, stride = _host(x)[0], strides[f]
+        else:
+            address, stride, _ = _host_rows(x, params[f].interleave_mode == 0)
+        sources[f] = FrameSource(params[f], address, int(stride), 0, int(max_stream_bytes[f]) if max_stream_bytes is not None else 0)
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    sizes = np.zeros(count, dtype=np.uint64)
+    errcs = np.zeros(count, dtype=np.int32)
+    address, nbytes = _host_contiguous(packed)
+    u64p = C.POINTER(C.c_uint64)
+    rc = l.charls_amd_encode_batch_host_ragged(count, sources, address, nbytes if capacity is None else int(capacity), alignment,
+                                               offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p), errcs.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_encode_batch_host_ragged")
+    return PackedBatch(packed, offsets, sizes, errcs)
+
+
+def decode_batch_host_ragged(packed, offsets, sizes, outs, *, strides=None, capacities=None, lib=None):
+    """charls_amd_decode_batch_host_ragged: decode_batch_ragged with `packed` and outs[f] in HOST memory.  Returns (params --
+    one CodecParams per frame --, errcs)."""
+    l = _bind(lib or capi.load_product())
+    offsets, sizes, count = _tables(offsets, sizes)
+    assert len(outs) == count
+    dests = (FrameDest * max(count, 1))()
+    for f, x in enumerate(outs):
+        address, shape, byte_strides, item = _host(x)
+        extent = (sum((n - 1) * s for n, s in zip(shape, byte_strides)) + item) if all(shape) else 0  # to the end of the last row
+        if strides is not None:
+            stride = strides[f]
+        elif _is_contiguous(shape, byte_strides, item):
+            stride = 0
+        else:
+            assert len(shape) == 2 and byte_strides[1] == item, "a 3-D view: say its row stride (planar or interleaved?)"
+            stride = byte_strides[0]
+        dests[f] = FrameDest(address, int(capacities[f]) if capacities is not None else extent, int(stride), 0)
+    params = (CodecParams * max(count, 1))()
+    errcs = np.zeros(count, dtype=np.int32)
+    u64p = C.POINTER(C.c_uint64)
+    rc = l.charls_amd_decode_batch_host_ragged(count, _host_contiguous(packed)[0], offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p), dests,
+                                               params, errcs.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_decode_batch_host_ragged")
+    return params, errcs
+
+
+def _is_contiguous(shape, byte_strides, item):
+    expect = item
+    for n, s in zip(reversed(shape), reversed(byte_strides)):
+        if n != 1 and s != expect:
+            return False
+        expect *= n
+    return True
+
+
+def encode_batch_host(frames, packed, *, alignment=1, max_stream_bytes=0, capacity=None, bits_per_sample=8, component_count=1,
+                      interleave_mode=0, near_lossless=0, color_transformation=0, preset=(0, 0, 0, 0, 0), encoding_options=0,
+                      restart_interval=0, width=None, height=None, stride=0, frame_pitch=None, lib=None) -> PackedBatch:
+    """charls_amd_encode_batch_host: encode_batch_packed with `frames` -- (F, ...) as for encode_batch -- and `packed` in HOST
+    memory.  width / height / stride / frame_pitch: frames with padded rows, or at some pitch of a byte array."""
+    l = _bind(lib or capi.load_product())
+    address, shape, byte_strides, item = _host(frames)
+    assert _is_contiguous(shape, byte_strides, item)
+    count = shape[0]
+    if width is None or height is None:
+        height, width = (shape[-2], shape[-1]) if component_count == 1 or interleave_mode == 0 else (shape[1], shape[2])
+    if frame_pitch is None:
+        frame_pitch = byte_strides[0] if count else 0
+    p = codec_params(int(width), int(height), bits_per_sample, component_count, interleave_mode, near_lossless,
+                     color_transformation=color_transformation, preset=preset, encoding_options=encoding_options, restart_interval=restart_interval)
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    sizes = np.zeros(count, dtype=np.uint64)
+    errcs = np.zeros(count, dtype=np.int32)
+    to, nbytes = _host_contiguous(packed)
+    u64p = C.POINTER(C.c_uint64)
+    rc = l.charls_amd_encode_batch_host(C.byref(p), count, address, int(frame_pitch), int(stride), to, nbytes if capacity is None else int(capacity),
+                                        alignment, int(max_stream_bytes), offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p),
+                                        errcs.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_encode_batch_host")
+    return PackedBatch(packed, offsets, sizes, errcs)
+
+
+def decode_batch_host(packed, offsets, sizes, out, *, stride=0, frame_pitch=None, lib=None):
+    """charls_amd_decode_batch_host: decode_batch_packed with `packed` and `out` -- (F, ...) -- in HOST memory.  Returns
+    (params, errcs)."""
+    l = _bind(lib or capi.load_product())
+    offsets, sizes, count = _tables(offsets, sizes)
+    address, shape, byte_strides, item = _host(out)
+    assert _is_contiguous(shape, byte_strides, item)
+    if frame_pitch is None:
+        frame_pitch = byte_strides[0] if count else 0
+    errcs = np.zeros(count, dtype=np.int32)
+    p = CodecParams()
+    u64p = C.POINTER(C.c_uint64)
+    rc = l.charls_amd_decode_batch_host(count, _host_contiguous(packed)[0], offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p), address,
+                                        int(frame_pitch), int(stride), C.byref(p), errcs.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_decode_batch_host")
+    return p, errcs
 
 
 # ---- encoding to a byte budget (charls_amd.h part 2f): sizes without streams, NEAR picked per frame ------------------------

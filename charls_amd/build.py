@@ -47,6 +47,7 @@ SOURCES = [
     "host/batch_budget.cpp",
     "host/batch_salvage.cpp",
     "host/batch_salvage_index.cpp",
+    "host/batch_host.cpp",
     "host/multi_device.cpp",
 ]
 

@@ -42,6 +42,9 @@ enum Knob : int
     kIdleReleaseMs,         // CHARLS_AMD_IDLE_RELEASE_MS: what the host-pointer ABI keeps between calls is freed after this long without a call (0 = kept)
     kNearDecodePixels,      // CHARLS_AMD_NEAR_DECODE_PIXELS: 1 = near-lossless single-component / line-interleaved scans on the pixel kernels (until round 6)
     kPackPassFrames,        // CHARLS_AMD_PACK_PASS_FRAMES: frames per pass of charls_amd_encode_batch_device_packed (its staging slots)
+    kHostLanes,             // CHARLS_AMD_HOST_LANES: lanes (worker thread + stream) of the host-memory batch calls, 1..8
+    kHostWindowFrames,      // CHARLS_AMD_HOST_WINDOW_FRAMES: most frames per window of the host-memory batch calls
+    kHostStageBytes,        // CHARLS_AMD_HOST_STAGE_BYTES: pinned staging per lane for pageable caller memory
     kCount
 };
 
@@ -53,7 +56,7 @@ inline const char* name_of(int k)
                                               "JOB_EVENTS", "WARM_EVENTS", "RUN_JOB_EVENTS", "RUN_WARM_EVENTS", "RARE_WARM_EVENTS",
                                               "TILE_SAMPLES", "PIXEL_MODE", "SPEC_CHUNK", "SPEC_WARM", "BATCH_ROUNDS", "COALESCE",
                                               "COALESCE_WAIT_US", "DECODE_WAVES_PER_CU", "DECODE_WORKGROUP_WAVES", "TRACE", "IDLE_RELEASE_MS", "NEAR_DECODE_PIXELS",
-                                              "PACK_PASS_FRAMES"};
+                                              "PACK_PASS_FRAMES", "HOST_LANES", "HOST_WINDOW_FRAMES", "HOST_STAGE_BYTES"};
     return k >= 0 && k < kCount ? names[k] : nullptr;
 }
 

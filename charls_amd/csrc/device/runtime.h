@@ -53,11 +53,13 @@ public:
     PinnedBuffer& operator=(const PinnedBuffer&) = delete;
     ~PinnedBuffer();
     void* ensure(size_t bytes);
+    void release() noexcept;
     template <typename T>
     T* as() const noexcept
     {
         return static_cast<T*>(ptr_);
     }
+    size_t capacity() const noexcept { return cap_; }
 
 private:
     void* ptr_{};
@@ -197,6 +199,13 @@ size_t work_area_bytes() noexcept;
 size_t thread_work_area_bytes() noexcept;   // the calling thread's own areas (not the shared set of the host-pointer ABI)
 void release_thread_work_areas() noexcept;
 size_t work_area_budget() noexcept; // what the calling thread's work areas may grow to right now (limit, free memory)
+// A share of the limit for the calling thread alone (0: none, the process-wide rule applies): while it is set,
+// workspace_limit() and work_area_budget() on this thread answer with it where it is the smaller.  The lanes of the
+// host-memory batch calls (host/batch_host.cpp) hand the device calls they make their part of the one limit this way.
+void set_thread_workspace_limit(uint64_t bytes) noexcept;
+// work_area_budget() for a caller whose memory is held by other threads as well (the lanes): `held_elsewhere` bytes of
+// device memory count as reachable, as the calling thread's own areas do.
+size_t work_area_budget_beside(size_t held_elsewhere) noexcept;
 // Scans the lossless pipeline was eligible for that were coded by the one-wavefront kernel because no work area could be had.
 uint64_t pipeline_fallback_scans() noexcept;
 uint64_t exact_retry_scans() noexcept; // scans the speed-path decoders handed to the exact decoder since the library was loaded

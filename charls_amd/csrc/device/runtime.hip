@@ -202,8 +202,15 @@ void DeviceBuffer::release() noexcept
 
 PinnedBuffer::~PinnedBuffer()
 {
+    release();
+}
+
+void PinnedBuffer::release() noexcept
+{
     if (ptr_)
         (void)hipHostFree(ptr_);
+    ptr_ = nullptr;
+    cap_ = 0;
 }
 
 void* PinnedBuffer::ensure(size_t bytes)
@@ -234,9 +241,21 @@ void set_workspace_limit(uint64_t bytes) noexcept
     g_workspace_limit.store(bytes);
 }
 
+namespace {
+thread_local uint64_t t_workspace_limit = 0; // set_thread_workspace_limit: this thread's share of the limit
+} // namespace
+
+void set_thread_workspace_limit(uint64_t bytes) noexcept
+{
+    t_workspace_limit = bytes;
+}
+
 uint64_t workspace_limit() noexcept
 {
-    return g_workspace_limit.load();
+    const uint64_t configured = g_workspace_limit.load();
+    if (t_workspace_limit == 0)
+        return configured;
+    return configured != 0 ? std::min(configured, t_workspace_limit) : t_workspace_limit;
 }
 
 Timings& last_timings() noexcept
@@ -317,7 +336,7 @@ size_t arena_budget(size_t held)
         (void)hipGetLastError();
         return size_t{1} << 30;
     }
-    const uint64_t configured = g_workspace_limit.load();
+    const uint64_t configured = workspace_limit(); // (with the calling thread's share, where it has one)
     const size_t limit = configured != 0 ? static_cast<size_t>(configured) : total_bytes / 4;
     const size_t reachable = free_bytes + held;
     const size_t usable = reachable > kArenaReserve ? reachable - kArenaReserve : reachable / 2;
@@ -359,6 +378,11 @@ DeviceBuffer& seek_arena(int which)
 size_t work_area_budget() noexcept
 {
     return arena_budget(areas().bytes());
+}
+
+size_t work_area_budget_beside(size_t held_elsewhere) noexcept
+{
+    return arena_budget(areas().bytes() + held_elsewhere);
 }
 
 size_t shared_areas_keep_bytes() noexcept

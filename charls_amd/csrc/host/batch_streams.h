@@ -77,6 +77,10 @@ EncodePlan plan_encode(const charls_amd_codec_params& params, size_t frame_bytes
 // charls_jpegls_encoder_get_estimated_destination_size for the frames of `p` (batch_packed.cpp).
 size_t estimated_stream_bytes(const charls_amd_codec_params& p);
 
+// What the lanes of the host-memory calls (batch_host.cpp; charls_amd.h part 2i) hold, device and pinned, given back: the
+// lanes' part of charls_amd_release_work_areas.  A call that runs on them finishes first; the lane threads stay.
+void release_host_lanes() noexcept;
+
 // offset_alignment of the packed calls: a power of two in [1, 4096].
 inline void check_offset_alignment(uint32_t alignment)
 {

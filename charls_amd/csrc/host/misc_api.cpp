@@ -5,6 +5,7 @@
 
 #include "../device/knobs.h"
 #include "../device/runtime.h"
+#include "batch_streams.h"
 #include "common.h"
 #include "scan_engine.h"
 
@@ -163,6 +164,7 @@ charls_jpegls_errc charls_amd_release_work_areas(void)
 {
     dev::release_work_areas();
     release_idle_engine_resources(); // the device buffers, streams and staging areas that handles share (scan_engine.h)
+    release_host_lanes();            // what the lanes of the host-memory batch calls hold (batch_host.cpp)
     return CHARLS_JPEGLS_ERRC_SUCCESS;
 }
 

@@ -821,6 +821,73 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_jpegls_decoder_decode_to_buffer_sal
     charls_amd_salvage_report* report, uint8_t* interval_status, size_t status_capacity);
 CHARLS_AMD_API int32_t charls_amd_salvage_index_counters(uint64_t* out, int32_t capacity);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Part 2i -- the batch API on HOST memory: frames and streams in the caller's host memory, one call, the PCIe copies
+ * overlapped with the coding inside it.  Every pointer below is a HOST pointer (the d_pixels members of
+ * charls_amd_frame_source / charls_amd_frame_dest too); there is no hip_stream argument and the calls return when the
+ * results are in the caller's memory.  The device is the calling thread's current device.  New entry points; nothing else
+ * changes, and the multi-device calls of part 2b stay as they are.
+ *
+ * Results: frame for frame what the device calls of part 2e give on device copies of the same data -- the same offsets
+ * (with the zeroed alignment gaps), sizes, stream bytes, errcs, params_out and pixels.  The capacity rule holds in the
+ * caller's order: a frame whose end lies beyond packed_capacity_bytes is destination_too_small and so is every frame
+ * behind it, whichever part of the batch was coded first.  One frame's failure changes no other frame's result.  Decode
+ * writes only the row bytes of each destination -- stride padding and everything outside a frame's extent stay as they
+ * were -- and nothing at all of a frame that fails; encode never writes to a source; nothing is written at or beyond
+ * packed_capacity_bytes.
+ * Whole-call errors are those of part 2e (NULL tables, a `reserved` that is not 0, a NULL pixel pointer, an
+ * offset_alignment that is no power of two in [1, 4096]); all are found before a device is asked for, and nothing is
+ * written then.  frame_count == 0 is success, with offsets[0] = 0 on encode.
+ * Host memory of any kind works, mixed within one call, at any base address: memory pinned by charls_amd_host_alloc, by
+ * charls_amd_host_register or by someone else's hipHostMalloc / hipHostRegister is copied from and to directly; pageable
+ * memory goes through pinned staging buffers of the library (bounded: CHARLS_AMD_HOST_STAGE_BYTES per lane, 64 MiB by
+ * default) at the price of one more copy on the host.
+ * Threading: the calls may be made from several threads; calls on one device take turns.
+ * How: the frames are walked in the caller's order in windows; a few LANES -- persistent worker threads of the library
+ * bound to the device, each with a stream and buffers of its own -- serve the windows round-robin, so that one window's
+ * copies run under another window's coding.  Encode brings the rows up packed (stride padding never crosses PCIe), codes a
+ * window with charls_amd_encode_batch_device_ragged and brings its streams down with one copy; decode parses the headers on
+ * the host, sends exactly sizes[f] bytes per stream, decodes with charls_amd_decode_batch_device_ragged and writes the rows
+ * at the caller's stride.  Memory: what the lanes hold on the device -- frames, streams, and the work areas of the device
+ * calls they make -- stays within charls_amd_set_workspace_limit, all lanes together; not_enough_memory when a configured
+ * limit cannot hold the largest single frame.  charls_amd_release_work_areas also releases what the lanes hold, device and
+ * pinned (the threads stay).  Knobs: HOST_LANES, HOST_WINDOW_FRAMES, HOST_STAGE_BYTES.
+ *
+ * host_alloc / host_free / host_register / host_unregister: pinned memory for callers without a HIP header.  Without a
+ *   usable device: NULL / CHARLS_AMD_ERRC_DEVICE_UNAVAILABLE.  host_free(NULL) is a no-op.  Registering pins whole PAGES:
+ *   register memory whose pages are the caller's alone (a mapping, a page-aligned allocation), not an object in the middle
+ *   of a heap page that other objects share, and unregister it before the memory goes back to its allocator.
+ * probe_batch_host_packed: the contract of charls_amd_probe_batch_device_packed on host bytes; needs no GPU, asks for none.
+ * encode_batch_host_ragged / decode_batch_host_ragged: the calls of part 2e with host tables AND host data.
+ * encode_batch_host / decode_batch_host: one geometry, frame f at frames + f * frame_pitch_bytes; the argument lists of
+ *   charls_amd_encode_batch_device_packed / charls_amd_decode_batch_device_packed without hip_stream (params_out: ONE element).
+ * host_counters, process-wide since the library was loaded: out[0] host batch calls, out[1] windows, out[2] bytes copied
+ *   host to device, out[3] device to host, out[4] bytes of pageable caller memory that went through the staging buffers,
+ *   out[5] device bytes the lanes hold now, out[6] pinned bytes the lanes hold now.  Returns the number of values (7 at most).
+ * ---------------------------------------------------------------------------------------------------------------- */
+CHARLS_AMD_API void* charls_amd_host_alloc(size_t size_bytes);
+CHARLS_AMD_API void charls_amd_host_free(void* memory);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_host_register(void* memory, size_t size_bytes);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_host_unregister(void* memory);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_probe_batch_host_packed(uint32_t frame_count, const void* packed, const uint64_t* offsets,
+                                                                     const uint64_t* sizes, charls_amd_codec_params* params_out,
+                                                                     uint64_t* frame_bytes_out, charls_jpegls_errc* errcs);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_encode_batch_host_ragged(uint32_t frame_count, const charls_amd_frame_source* sources,
+                                                                      void* packed, size_t packed_capacity_bytes, uint32_t offset_alignment,
+                                                                      uint64_t* offsets, uint64_t* sizes, charls_jpegls_errc* errcs);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_host_ragged(uint32_t frame_count, const void* packed, const uint64_t* offsets,
+                                                                      const uint64_t* sizes, const charls_amd_frame_dest* dests,
+                                                                      charls_amd_codec_params* params_out, charls_jpegls_errc* errcs);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_encode_batch_host(const charls_amd_codec_params* params, uint32_t frame_count,
+                                                               const void* frames, size_t frame_pitch_bytes, uint32_t stride, void* packed,
+                                                               size_t packed_capacity_bytes, uint32_t offset_alignment,
+                                                               size_t max_stream_bytes, uint64_t* offsets, uint64_t* sizes,
+                                                               charls_jpegls_errc* errcs);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_host(uint32_t frame_count, const void* packed, const uint64_t* offsets,
+                                                               const uint64_t* sizes, void* frames, size_t frame_pitch_bytes, uint32_t stride,
+                                                               charls_amd_codec_params* params_out, charls_jpegls_errc* errcs);
+CHARLS_AMD_API int32_t charls_amd_host_counters(uint64_t* out, int32_t capacity);
+
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */
 CHARLS_AMD_API charls_jpegls_errc charls_amd_set_encode_engine(int32_t engine);
