@@ -147,6 +147,16 @@ def _bind(lib):
         l.charls_amd_decode_batch_host.restype = C.c_int32
         l.charls_amd_host_counters.argtypes = [u64p, C.c_int32]
         l.charls_amd_host_counters.restype = C.c_int32
+    if hasattr(l, "charls_amd_transcode_batch_device"):  # (part 2j; an A/B tool may load a build from before it)
+        spec_p = C.POINTER(capi.TranscodeSpec)
+        l.charls_amd_transcode_batch_device.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, spec_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                        C.c_uint32, u64p, u64p, C.POINTER(CodecParams), i32p, C.c_void_p]
+        l.charls_amd_transcode_batch_device.restype = C.c_int32
+        l.charls_amd_transcode_batch_host.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, spec_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                      C.c_uint32, u64p, u64p, C.POINTER(CodecParams), i32p]
+        l.charls_amd_transcode_batch_host.restype = C.c_int32
+        l.charls_amd_transcode_counters.argtypes = [u64p, C.c_int32]
+        l.charls_amd_transcode_counters.restype = C.c_int32
     l._batch_bound = True
     return l
 
@@ -877,6 +887,69 @@ def decode_batch_host(packed, offsets, sizes, out, *, stride=0, frame_pitch=None
     if rc != 0:
         raise capi.JpegLSError(rc, "charls_amd_decode_batch_host")
     return p, errcs
+
+
+# ---- re-coding a packed blob (charls_amd.h part 2j): decode and encode again in one call, restart intervals / NEAR replaced --
+
+@dataclass
+class TranscodedBatch:
+    packed: object           # the output blob (a device tensor, or host memory); frame f's .jls is packed[offsets[f]:offsets[f] + sizes[f]]
+    offsets: np.ndarray      # uint64, host, frames + 1 elements; offsets[-1] is the total
+    sizes: np.ndarray        # uint64, host
+    errcs: np.ndarray        # int32, host
+    params: object           # ctypes array, one CodecParams per frame: what frame f was coded with
+
+
+def _transcode_tables(offsets, sizes, specs):
+    offsets, sizes, count = _tables(offsets, sizes)
+    if isinstance(specs, capi.TranscodeSpec):
+        specs = [specs]
+    table = (capi.TranscodeSpec * max(len(specs), 1))(*specs)
+    return offsets, sizes, count, table, len(specs)
+
+
+def transcode_batch(packed_in, offsets, sizes, specs, packed_out, *, alignment=1, capacity=None, lib=None) -> TranscodedBatch:
+    """charls_amd_transcode_batch_device: every stream packed_in[offsets[f]:offsets[f] + sizes[f]] decoded and coded again into
+    `packed_out` (1-D uint8 device tensors) with the fields replaced that specs names (capi.transcode_spec: one for every
+    frame, or a list with one per frame)."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert packed_in.is_cuda and packed_in.is_contiguous() and packed_out.is_cuda and packed_out.is_contiguous()
+    offsets, sizes, count, table, spec_count = _transcode_tables(offsets, sizes, specs)
+    offsets_out = np.zeros(count + 1, dtype=np.uint64)
+    sizes_out = np.zeros(count, dtype=np.uint64)
+    errcs = np.zeros(count, dtype=np.int32)
+    params = (CodecParams * max(count, 1))()
+    stream = torch.cuda.current_stream(packed_in.device).cuda_stream
+    u64p = C.POINTER(C.c_uint64)
+    rc = l.charls_amd_transcode_batch_device(count, packed_in.data_ptr(), offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p), table,
+                                             spec_count, packed_out.data_ptr(), packed_out.numel() if capacity is None else int(capacity),
+                                             alignment, offsets_out.ctypes.data_as(u64p), sizes_out.ctypes.data_as(u64p), params,
+                                             errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_transcode_batch_device")
+    return TranscodedBatch(packed_out, offsets_out, sizes_out, errcs, params)
+
+
+def transcode_batch_host(packed_in, offsets, sizes, specs, packed_out, *, alignment=1, capacity=None, lib=None) -> TranscodedBatch:
+    """charls_amd_transcode_batch_host: transcode_batch with both blobs in HOST memory (numpy arrays or CPU tensors, pinned or
+    pageable)."""
+    l = _bind(lib or capi.load_product())
+    offsets, sizes, count, table, spec_count = _transcode_tables(offsets, sizes, specs)
+    offsets_out = np.zeros(count + 1, dtype=np.uint64)
+    sizes_out = np.zeros(count, dtype=np.uint64)
+    errcs = np.zeros(count, dtype=np.int32)
+    params = (CodecParams * max(count, 1))()
+    to, nbytes = _host_contiguous(packed_out)
+    u64p = C.POINTER(C.c_uint64)
+    rc = l.charls_amd_transcode_batch_host(count, _host_contiguous(packed_in)[0], offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p), table,
+                                           spec_count, to, nbytes if capacity is None else int(capacity), alignment,
+                                           offsets_out.ctypes.data_as(u64p), sizes_out.ctypes.data_as(u64p), params,
+                                           errcs.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_transcode_batch_host")
+    return TranscodedBatch(packed_out, offsets_out, sizes_out, errcs, params)
 
 
 # ---- encoding to a byte budget (charls_amd.h part 2f): sizes without streams, NEAR picked per frame ------------------------

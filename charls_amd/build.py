@@ -48,6 +48,7 @@ SOURCES = [
     "host/batch_salvage.cpp",
     "host/batch_salvage_index.cpp",
     "host/batch_host.cpp",
+    "host/batch_transcode.cpp",
     "host/multi_device.cpp",
 ]
 

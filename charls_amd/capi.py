@@ -56,6 +56,32 @@ class SalvageReport(C.Structure):  # charls_amd_salvage_report (include/charls_a
         return (self.state, self.intervals, self.intervals_lost, self.rows_lost, self.first_lost_row, self.reserved)
 
 
+TRANSCODE_NEAR, TRANSCODE_RESTART_INTERVAL, TRANSCODE_PRESET, TRANSCODE_ENCODING_OPTIONS = 1, 2, 4, 8
+
+
+class TranscodeSpec(C.Structure):  # charls_amd_transcode_spec (include/charls_amd.h part 2j; product library only)
+    _fields_ = [("set", C.c_uint32), ("near_lossless", C.c_int32), ("restart_interval", C.c_uint32),
+                ("preset_coding_parameters", PcParameters), ("encoding_options", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def transcode_spec(near_lossless=None, restart_interval=None, preset=None, encoding_options=None) -> TranscodeSpec:
+    """A spec that replaces exactly the fields given (None: the source stream's value stays)."""
+    s = TranscodeSpec()
+    if near_lossless is not None:
+        s.set |= TRANSCODE_NEAR
+        s.near_lossless = int(near_lossless)
+    if restart_interval is not None:
+        s.set |= TRANSCODE_RESTART_INTERVAL
+        s.restart_interval = int(restart_interval)
+    if preset is not None:
+        s.set |= TRANSCODE_PRESET
+        s.preset_coding_parameters = PcParameters(*preset)
+    if encoding_options is not None:
+        s.set |= TRANSCODE_ENCODING_OPTIONS
+        s.encoding_options = int(encoding_options)
+    return s
+
+
 class MappingTableInfo(C.Structure):  # include/charls/public_types.h:1024-1034 (12 bytes)
     _fields_ = [("table_id", C.c_int32), ("entry_size", C.c_int32), ("data_size", C.c_uint32)]
 
@@ -490,3 +516,15 @@ def index_counters(lib: CharLSLibrary | None = None) -> dict:
     out = (C.c_uint64 * 3)()
     n = L.charls_amd_index_counters(out, 3)
     return dict(zip(("scans_from_points", "intervals", "fallback_scans")[:n], (int(v) for v in out[:n])))
+
+
+def transcode_counters(lib: CharLSLibrary | None = None) -> tuple:
+    """charls_amd_transcode_counters: (frames re-coded, windows, frames refused for a mapping table, frames behind the one that
+    met the capacity), process-wide since the library was loaded.  The calls themselves: batch.transcode_batch / _host."""
+    L = (lib or load_product()).lib
+    L.charls_amd_transcode_counters.argtypes = [C.POINTER(C.c_uint64), C.c_int32]
+    L.charls_amd_transcode_counters.restype = C.c_int32
+    out = (C.c_uint64 * 4)()
+    n = L.charls_amd_transcode_counters(out, 4)
+    assert n == 4
+    return tuple(int(v) for v in out)

@@ -45,6 +45,7 @@ enum Knob : int
     kHostLanes,             // CHARLS_AMD_HOST_LANES: lanes (worker thread + stream) of the host-memory batch calls, 1..8
     kHostWindowFrames,      // CHARLS_AMD_HOST_WINDOW_FRAMES: most frames per window of the host-memory batch calls
     kHostStageBytes,        // CHARLS_AMD_HOST_STAGE_BYTES: pinned staging per lane for pageable caller memory
+    kTranscodeWindowFrames, // CHARLS_AMD_TRANSCODE_WINDOW_FRAMES: frames per window of charls_amd_transcode_batch_device (its frame area)
     kCount
 };
 
@@ -56,7 +57,8 @@ inline const char* name_of(int k)
                                               "JOB_EVENTS", "WARM_EVENTS", "RUN_JOB_EVENTS", "RUN_WARM_EVENTS", "RARE_WARM_EVENTS",
                                               "TILE_SAMPLES", "PIXEL_MODE", "SPEC_CHUNK", "SPEC_WARM", "BATCH_ROUNDS", "COALESCE",
                                               "COALESCE_WAIT_US", "DECODE_WAVES_PER_CU", "DECODE_WORKGROUP_WAVES", "TRACE", "IDLE_RELEASE_MS", "NEAR_DECODE_PIXELS",
-                                              "PACK_PASS_FRAMES", "HOST_LANES", "HOST_WINDOW_FRAMES", "HOST_STAGE_BYTES"};
+                                              "PACK_PASS_FRAMES", "HOST_LANES", "HOST_WINDOW_FRAMES", "HOST_STAGE_BYTES",
+                                              "TRANSCODE_WINDOW_FRAMES"};
     return k >= 0 && k < kCount ? names[k] : nullptr;
 }
 

@@ -189,6 +189,9 @@ DeviceBuffer& plane_arena(); // the calling thread's private stream buffers of t
 // The calling thread's staging slots of charls_amd_encode_batch_device_packed (host/batch_packed.cpp): a pass of frames is
 // coded into them and packed from them (a work area: counted by work_area_bytes, freed by release_work_areas).
 DeviceBuffer& pack_arena();
+// The calling thread's frames of charls_amd_transcode_batch_device (host/batch_transcode.cpp): a window of streams is decoded
+// into them and coded again from them (a work area: counted by work_area_bytes, freed by release_work_areas).
+DeviceBuffer& transcode_arena();
 // The calling thread's buffers of the seek-point index's batch calls (host/batch_index.cpp): seek points, work items, descs,
 // results, hash jobs (work areas: counted by work_area_bytes, freed by release_work_areas).
 constexpr int kSeekArenas = 6;

@@ -370,6 +370,11 @@ DeviceBuffer& pack_arena()
     return work_buffer(WorkBuffer::pack);
 }
 
+DeviceBuffer& transcode_arena()
+{
+    return work_buffer(WorkBuffer::transcode);
+}
+
 DeviceBuffer& seek_arena(int which)
 {
     return areas().buffers[static_cast<int>(WorkBuffer::seek_first) + which];

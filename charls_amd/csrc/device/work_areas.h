@@ -18,6 +18,7 @@ enum class WorkBuffer : int
     pipeline, // the tile pipeline's arena
     plane,    // private stream buffers of the planar batch encoder
     pack,     // staging slots of the packed batch encoder
+    transcode, // decoded frames of a window of charls_amd_transcode_batch_device
     // restart-interval decode (launch_decode_intervals) and encode (launch_encode_intervals)
     marks,
     counts,

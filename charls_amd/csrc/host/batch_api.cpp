@@ -733,6 +733,15 @@ void jls::decode_batch_streams(uint32_t frame_count, const void* d_streams, cons
     decode_by_rounds(b);
     for (uint32_t i = 0; i < frame_count; ++i)
         errcs[i] = win.fr[i].errc;
+    if (to.names_table_out != nullptr)
+        for (uint32_t i = 0; i < frame_count; ++i)
+        { // (the reader keeps, per component, the table id of the scan header that named it)
+            const StreamReader& reader = win.fr[i].reader;
+            to.names_table_out[i] = 0;
+            for (size_t c = 0; c < reader.component_count(); ++c)
+                if (reader.mapping_table_id(c) != 0)
+                    to.names_table_out[i] = 1;
+        }
     dev::Timings& t = dev::last_timings();
     t.values[0] = launcher.gpu_ms();
     t.values[1] = launcher.gpu_ms();

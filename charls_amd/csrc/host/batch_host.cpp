@@ -756,6 +756,112 @@ void decode_host_ragged(uint32_t frame_count, const void* packed, const uint64_t
         raise(rc);
 }
 
+// charls_amd_transcode_batch_host (charls_amd.h part 2j): the windows one after another on ONE lane -- streams up, the device
+// call's body (batch_transcode.cpp: transcode_frames) on the device window, the front of its blob down.  Nothing runs under
+// anything: a window's copies are two streams per frame, its decode is a dependency chain per frame.
+void transcode_host(uint32_t frame_count, const void* packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
+                    const charls_amd_transcode_spec* specs, uint32_t spec_count, void* packed_out, size_t capacity, uint32_t alignment,
+                    uint64_t* offsets_out, uint64_t* sizes_out, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs)
+{
+    // ---- the headers, where the bytes are: what every frame will be coded with, the room its stream may take in the device
+    // window, and what the device call needs for it in its own areas
+    const auto* in = static_cast<const uint8_t*>(packed_in);
+    std::vector<charls_amd_codec_params> coded_with(frame_count); // (zeroed where the header does not parse or holds no frame)
+    std::vector<uint64_t> slot(frame_count, 0), weights(frame_count, 0);
+    uint64_t largest = 0;
+    for (uint32_t f = 0; f < frame_count; ++f)
+    {
+        try
+        {
+            StreamReader reader;
+            reader.set_source(in + offsets_in[f], static_cast<size_t>(sizes_in[f]));
+            reader.read_header();
+            if (!reader.end_of_image())
+            {
+                const charls_frame_info& fi = reader.frame_info();
+                const size_t bytes = checked_mul(checked_mul(checked_mul(static_cast<size_t>(fi.component_count), fi.height), fi.width),
+                                                 bytes_per_sample(fi.bits_per_sample));
+                coded_with[f] = transcode_params(params_of(reader), specs[spec_count == 1 ? 0 : f]);
+                slot[f] = hs::round_up(estimated_stream_bytes(coded_with[f]), alignment);
+                largest = std::max<uint64_t>(largest, std::max<uint64_t>(slot[f], bytes));
+            }
+        }
+        catch (const error&)
+        { // (the device call reports it)
+            coded_with[f] = charls_amd_codec_params{};
+        }
+        weights[f] = align_up(static_cast<size_t>(sizes_in[f]), 16) + 16 + align_up(static_cast<size_t>(slot[f]), 16);
+    }
+    Shape shape;
+    shape.budget = dev::work_area_budget_beside(lanes_hold());
+    shape.lanes = 1;
+    shape.own = shape.budget / 2; // (the lane's two blobs; the device call's areas get the other half)
+    shape.thread_limit = std::max<size_t>(shape.budget - shape.own, 1);
+    shape.stage_bytes = static_cast<size_t>(std::max<long long>(knobs::get_or(knobs::kHostStageBytes, kDefaultStageBytes), kMinStageBytes));
+    if (dev::workspace_limit() != 0 && largest > shape.thread_limit)
+        raise(CHARLS_JPEGLS_ERRC_NOT_ENOUGH_MEMORY);
+    const long long forced_window = knobs::get_or(knobs::kHostWindowFrames, 0);
+    shape.window_end = hs::plan_windows(weights, forced_window >= 1 ? static_cast<uint32_t>(std::min<long long>(forced_window, UINT32_MAX)) : frame_count,
+                                        shape.own);
+    auto* out = static_cast<uint8_t*>(packed_out);
+    hs::Carry carry{0, false}; // (one lane: its windows run in their order)
+
+    auto window = [&](Lane& lane, uint32_t w) {
+        const uint32_t first = w == 0 ? 0 : shape.window_end[w - 1], last = shape.window_end[w], n = last - first;
+        if (carry.full)
+        { // (behind the capacity: nothing of the window goes up)
+            for (uint32_t f = first; f < last; ++f)
+            {
+                offsets_out[f] = carry.at;
+                sizes_out[f] = 0;
+                params_out[f] = coded_with[f];
+                errcs[f] = CHARLS_JPEGLS_ERRC_DESTINATION_TOO_SMALL;
+            }
+            transcode_count_behind_capacity(n);
+            return;
+        }
+        Copier copy{lane, shape.stage_bytes, nullptr};
+        // (+ 32: the decoders load whole aligned 16-byte groups; the margin behind the last stream is part of the allocation)
+        size_t in_bytes = 32, out_bytes = 0;
+        for (uint32_t f = first; f < last; ++f)
+        {
+            in_bytes += align_up(static_cast<size_t>(sizes_in[f]), 16);
+            out_bytes += static_cast<size_t>(slot[f]);
+        }
+        auto* d_in = static_cast<uint8_t*>(lane.blob.ensure(in_bytes));
+        auto* d_out = static_cast<uint8_t*>(lane.frames.ensure(out_bytes + 16));
+        lane.account();
+        std::vector<uint64_t> w_offsets_in(n), w_offsets_out(static_cast<size_t>(n) + 1);
+        size_t stream_at = 0;
+        for (uint32_t k = 0; k < n; ++k)
+        {
+            const uint32_t f = first + k;
+            copy.up(d_in + stream_at, in + offsets_in[f], static_cast<size_t>(sizes_in[f]), static_cast<size_t>(sizes_in[f]), 1);
+            w_offsets_in[k] = stream_at;
+            stream_at += align_up(static_cast<size_t>(sizes_in[f]), 16);
+        }
+        hip_check(hipStreamSynchronize(lane.stream)); // (the device call works on side streams too: the streams are there first)
+        // Every stream fits the room its slot gives it, so the window's blob is as large as the caller's buffer needs it to be:
+        // what is left of the capacity decides exactly as it does in one call over all frames.
+        const uint64_t room = std::min<uint64_t>(out_bytes, capacity - std::min<uint64_t>(carry.at, capacity));
+        const uint32_t beyond = transcode_frames(n, d_in, w_offsets_in.data(), sizes_in + first, specs + (spec_count == 1 ? 0 : first),
+                                                 spec_count == 1 ? 1 : n, d_out, static_cast<size_t>(room), alignment, w_offsets_out.data(),
+                                                 sizes_out + first, params_out + first, errcs + first, lane.stream);
+        for (uint32_t k = 0; k < n; ++k)
+            offsets_out[first + k] = carry.at + w_offsets_out[k];
+        const size_t front = static_cast<size_t>(std::min<uint64_t>(w_offsets_out[n], room)); // (the zeros behind the last frame stop at the capacity)
+        if (front != 0)
+            copy.down(d_out, out + carry.at, front, front, 1);
+        hip_check(hipStreamSynchronize(lane.stream));
+        carry.at += w_offsets_out[n];
+        carry.full = beyond != n;
+    };
+    const charls_jpegls_errc rc = on_lanes(shape, window, [] {});
+    if (rc != CHARLS_JPEGLS_ERRC_SUCCESS)
+        raise(rc);
+    offsets_out[frame_count] = carry.at;
+}
+
 } // namespace
 
 // charls_amd_release_work_areas (misc_api.cpp): what the lanes hold, device and pinned.  The threads stay.
@@ -1028,6 +1134,31 @@ try
                 break;
             }
     }
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}
+
+// ---- part 2j on host blobs
+extern "C" charls_jpegls_errc charls_amd_transcode_batch_host(uint32_t frame_count, const void* packed_in, const uint64_t* offsets_in,
+                                                              const uint64_t* sizes_in, const charls_amd_transcode_spec* specs, uint32_t spec_count,
+                                                              void* packed_out, size_t packed_capacity_bytes, uint32_t offset_alignment,
+                                                              uint64_t* offsets_out, uint64_t* sizes_out, charls_amd_codec_params* params_out,
+                                                              charls_jpegls_errc* errcs)
+try
+{
+    check_transcode_call(frame_count, packed_in, offsets_in, sizes_in, specs, spec_count, packed_out, offset_alignment, offsets_out, sizes_out,
+                         params_out, errcs);
+    if (frame_count == 0)
+    {
+        offsets_out[0] = 0;
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    }
+    dev::require_device();
+    transcode_host(frame_count, packed_in, offsets_in, sizes_in, specs, spec_count, packed_out, packed_capacity_bytes, offset_alignment,
+                   offsets_out, sizes_out, params_out, errcs);
     return CHARLS_JPEGLS_ERRC_SUCCESS;
 }
 catch (...)

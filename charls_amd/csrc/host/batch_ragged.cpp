@@ -127,6 +127,17 @@ try
     }
     check_pointer(d_packed);
     dev::require_device();
+    encode_ragged_frames(frame_count, sources, d_packed, packed_capacity_bytes, offset_alignment, offsets, sizes, errcs, hip_stream);
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}
+
+uint32_t jls::encode_ragged_frames(uint32_t frame_count, const charls_amd_frame_source* sources, void* d_packed, size_t packed_capacity_bytes,
+                                   uint32_t offset_alignment, uint64_t* offsets, uint64_t* sizes, charls_jpegls_errc* errcs, void* hip_stream)
+{
     auto stream = static_cast<hipStream_t>(hip_stream);
 
     // ---- every frame's own verdict and slot size.  A frame the encoder refuses is not coded: the verdict is its errc.
@@ -208,6 +219,7 @@ try
     uint64_t at = 0;
     size_t job_count = 0;
     bool full = false; // a frame's end lay beyond the capacity: that frame and every frame after it get destination_too_small
+    uint32_t first_beyond = frame_count;
     for (uint32_t w = 0, first = 0; w < window_end.size(); first = window_end[w++])
     {
         const uint32_t last = window_end[w];
@@ -266,7 +278,10 @@ try
             offsets[f] = at;
             const bool coded = !full && errcs[f] == CHARLS_JPEGLS_ERRC_SUCCESS && sizes[f] != 0;
             if (coded && sizes[f] > packed_capacity_bytes - std::min<uint64_t>(at, packed_capacity_bytes))
+            {
                 full = true;
+                first_beyond = f;
+            }
             if (full)
             {
                 errcs[f] = CHARLS_JPEGLS_ERRC_DESTINATION_TOO_SMALL;
@@ -302,9 +317,5 @@ try
     t.values[0] = total_ms;
     t.values[1] = scan_ms;
     t.count = 2;
-    return CHARLS_JPEGLS_ERRC_SUCCESS;
-}
-catch (...)
-{
-    return current_exception_to_errc();
+    return first_beyond;
 }

@@ -23,6 +23,9 @@ struct BatchDests
     const charls_amd_frame_dest* dests;
     bool ragged;
     uint64_t* frame_bytes_out; // the probe only
+    // decode only, may be nullptr (HOST, one per frame): 1 where a scan header the decode read names a mapping table (a table
+    // id that is not 0 for any component), else 0 -- charls_amd_transcode_batch_device refuses such frames
+    uint8_t* names_table_out = nullptr;
 };
 
 // The batch decoder with every frame's stream named by an offset of its own: frame i's .jls is the sizes[i] bytes at
@@ -61,6 +64,12 @@ void decode_batch_salvage_indexed(uint32_t frame_count, const void* d_packed, co
 void encode_batch_frames(const charls_amd_codec_params& params, uint32_t frame_count, const uint8_t* const* d_pixels,
                          size_t frame_bytes, uint32_t stride_arg, void* d_streams, size_t stream_pitch_bytes, uint64_t* sizes,
                          charls_jpegls_errc* errcs, void* hip_stream);
+// The body of charls_amd_encode_batch_device_ragged (batch_ragged.cpp) behind its whole-call checks: frame_count >= 1, the
+// tables, every sources[f].d_pixels and d_packed are there, the alignment is valid, a device is.  Returns the first frame, in
+// the caller's order, whose end lay beyond packed_capacity_bytes -- that frame and every frame behind it have
+// destination_too_small --, or frame_count.
+uint32_t encode_ragged_frames(uint32_t frame_count, const charls_amd_frame_source* sources, void* d_packed, size_t packed_capacity_bytes,
+                              uint32_t offset_alignment, uint64_t* offsets, uint64_t* sizes, charls_jpegls_errc* errcs, void* hip_stream);
 // Raises what the batch encoder raises for these parameters before it codes anything (needs no GPU).
 void check_encode_params(const charls_amd_codec_params& params, size_t frame_bytes, uint32_t stride_arg);
 
@@ -76,6 +85,22 @@ EncodePlan plan_encode(const charls_amd_codec_params& params, size_t frame_bytes
 
 // charls_jpegls_encoder_get_estimated_destination_size for the frames of `p` (batch_packed.cpp).
 size_t estimated_stream_bytes(const charls_amd_codec_params& p);
+
+// charls_amd_transcode_batch_device (batch_transcode.cpp; charls_amd.h part 2j) in three pieces, which the host form
+// (batch_host.cpp) uses too: `p` with the fields that spec.set names replaced; the whole-call checks, which raise before a
+// device is asked for (the blobs are DEVICE pointers in one form and HOST pointers in the other: only looked at for NULL);
+// and the body behind them -- frame_count >= 1, a device is there --, which returns the first frame, in the caller's order,
+// whose end lay beyond packed_capacity_bytes, or frame_count.
+charls_amd_codec_params transcode_params(charls_amd_codec_params p, const charls_amd_transcode_spec& spec) noexcept;
+void check_transcode_call(uint32_t frame_count, const void* packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
+                          const charls_amd_transcode_spec* specs, uint32_t spec_count, const void* packed_out, uint32_t offset_alignment,
+                          const uint64_t* offsets_out, const uint64_t* sizes_out, const charls_amd_codec_params* params_out,
+                          const charls_jpegls_errc* errcs);
+uint32_t transcode_frames(uint32_t frame_count, const void* d_packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
+                          const charls_amd_transcode_spec* specs, uint32_t spec_count, void* d_packed_out, size_t packed_capacity_bytes,
+                          uint32_t offset_alignment, uint64_t* offsets_out, uint64_t* sizes_out, charls_amd_codec_params* params_out,
+                          charls_jpegls_errc* errcs, void* hip_stream);
+void transcode_count_behind_capacity(uint64_t frames) noexcept; // charls_amd_transcode_counters [3], for windows the host form does not send
 
 // What the lanes of the host-memory calls (batch_host.cpp; charls_amd.h part 2i) hold, device and pinned, given back: the
 // lanes' part of charls_amd_release_work_areas.  A call that runs on them finishes first; the lane threads stay.

@@ -888,6 +888,90 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_host(uint32_t frame_co
                                                                charls_amd_codec_params* params_out, charls_jpegls_errc* errcs);
 CHARLS_AMD_API int32_t charls_amd_host_counters(uint64_t* out, int32_t capacity);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Part 2j -- RE-CODING the streams of a packed blob in one call.  Only this library's encoder writes restart intervals; the
+ * streams callers already hold -- archives written by the reference, DICOM multi-frame pixel data -- have none, so they decode
+ * as one dependency chain each and part 2g cannot confine damage in them.  This call decodes every stream of a blob and codes
+ * it again with a few parameters replaced -- a restart interval added, NEAR raised for an archive tier -- without the caller
+ * owning the frames in between.  `offsets_in`, `sizes_in`, `specs`, `offsets_out` (frame_count + 1), `sizes_out`,
+ * `params_out` and `errcs` are HOST arrays; the blobs are DEVICE memory; the return value and hip_stream are those of part 2.
+ * specs: ONE element for every frame (spec_count == 1) or one per frame (spec_count == frame_count).
+ *
+ * The contract is a composition, byte for byte.  Frame f's output is what charls_amd_encode_batch_device_ragged writes for one
+ * source whose pixels are what charls_amd_decode_batch_device_ragged decodes from input stream f into a packed destination
+ * (stride 0), whose params are that decode's params_out[f] with the fields named by specs[f].set replaced, and whose
+ * max_stream_bytes is 0; params_out[f] is what the frame was coded with.  Placement is part 2d's offset rule in the caller's
+ * order, zeroed gaps included, and part 2d's capacity rule holds: a frame whose end lies beyond packed_capacity_bytes gets
+ * destination_too_small with sizes_out[f] == 0, and so does EVERY frame behind it in the caller's order, whatever it holds
+ * (those frames need not be decoded; params_out[f] is then the stream's parameters with the spec where its header can be
+ * read, else zeroed).  Nothing is written at or beyond packed_capacity_bytes.
+ * Failures of a frame: one whose decode fails keeps the decoder's code in errcs[f], has sizes_out[f] == 0, takes no room and
+ *   gets a zeroed params_out[f]; one the encoder refuses (a colour transformation with NEAR above 0, preset parameters that are
+ *   invalid for the frame, ...) gets the encoder's code.  One frame's failure never changes another frame's bytes, nor the
+ *   offset arithmetic beyond taking no room.
+ * Errors of the whole call, all checked before a device is asked for, nothing being written: NULL tables or blobs, a
+ *   spec_count that is neither 1 nor frame_count, a `set` bit that is not defined, a `reserved` that is not 0, an
+ *   offset_alignment that is no power of two in [1, 4096] (invalid_argument), an offsets_in[f] + sizes_in[f] that overflows
+ *   (invalid_argument_size).  frame_count == 0 is success with offsets_out[0] == 0.  The input and the output must not
+ *   overlap; this is not looked for.  The readability rule of part 2d applies to d_packed_in.
+ * What does not survive: the output container is the batch encoder's -- SOI, SOF55, LSE where the parameters are not the
+ *   defaults, DRI, the scans, EOI.  SPIFF headers, comments and application-data segments of the source are dropped, and a
+ *   height that came from a DNL segment is written into the frame header.  A frame one of whose scan headers names a mapping
+ *   table (a table id that is not 0 for any component) is refused with invalid_operation once it has decoded: the batch
+ *   encoder cannot write the table, and dropping the reference silently would change what the samples mean.
+ *   With set == 0 a LOSSLESS stream in that plain container comes back byte for byte, and with a new restart interval its
+ *   pixels are unchanged.  A near-lossless stream is coded near-lossless again: its pixels stay within its NEAR of what the
+ *   input decodes to, and even with set == 0 its bytes may change (where a reconstructed sample was clamped at 0 or MAXVAL the
+ *   second quantisation differs; the reference's encoder on the reference's decode does the same).
+ * How: one probe of the whole batch gives every frame's size.  The frames are then walked in the caller's order in WINDOWS:
+ *   the longest run of frames whose packed pixels, each frame rounded up to 256 bytes, fit one more work area of the calling
+ *   thread (at most a quarter of what its work areas may hold, see charls_amd_set_workspace_limit; counted by
+ *   charls_amd_work_area_bytes, freed by charls_amd_release_work_areas; the knob TRANSCODE_WINDOW_FRAMES forces the length).
+ *   A configured workspace limit that does not cover the largest frame, or its staging slot in the encoder, makes the call
+ *   return not_enough_memory before anything is written.  Per window: the ragged decode into the area, the ragged encode of
+ *   the frames that decoded at d_packed_out + base with what is left of the capacity, and base added to the offsets; base is
+ *   the end of the window before, a multiple of the alignment, so bytes, gaps and offsets are those of one encode over all
+ *   frames.  A frame's header is parsed twice, by the probe and by its window's decode.
+ * charls_amd_last_timings afterwards: [0] all launches, [1] their dominant kernels, [2] the decodes, [3] the encodes, ms.
+ * transcode_batch_host: the same arguments with both blobs in HOST memory of any kind (part 2i: pinned memory is copied from
+ *   and to directly, pageable memory goes through the lane's staging halves); the results are those of the device call on
+ *   device copies of the same bytes.  Windows run one after another on ONE lane of part 2i -- the streams up into a 16-byte
+ *   granular device window with its margin, the device call's body, the front of the window's blob down -- and nothing is
+ *   pipelined: a window's PCIe traffic is two streams per frame, its decode a dependency chain per frame.  Knobs:
+ *   HOST_WINDOW_FRAMES, HOST_STAGE_BYTES.
+ * transcode_counters, process-wide since the library was loaded: out[0] frames re-coded, out[1] windows of the device
+ *   call, out[2] frames refused for a mapping table, out[3] frames behind the one that met the capacity.  Returns the number
+ *   of values written (4 at most).
+ * Not done: the decode of window w + 1 does not run under the encode of window w (the group decoder takes 156 of a CU's
+ *   160 KB of LDS: the tile kernels cannot sit beside it); the interleave mode cannot be changed; the byte budget of part 2f
+ *   and the multi-device calls of part 2b are not joined to it.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define CHARLS_AMD_TRANSCODE_NEAR 1u
+#define CHARLS_AMD_TRANSCODE_RESTART_INTERVAL 2u
+#define CHARLS_AMD_TRANSCODE_PRESET 4u
+#define CHARLS_AMD_TRANSCODE_ENCODING_OPTIONS 8u
+typedef struct charls_amd_transcode_spec
+{
+    uint32_t set; /* which fields below replace the source stream's value; any other bit: invalid_argument */
+    int32_t near_lossless;
+    uint32_t restart_interval; /* lines; 0 removes restart intervals */
+    charls_jpegls_pc_parameters preset_coding_parameters;
+    charls_encoding_options encoding_options;
+    uint32_t reserved; /* must be 0 */
+} charls_amd_transcode_spec;
+
+CHARLS_AMD_API charls_jpegls_errc charls_amd_transcode_batch_device(
+    uint32_t frame_count, const void* d_packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
+    const charls_amd_transcode_spec* specs, uint32_t spec_count, void* d_packed_out, size_t packed_capacity_bytes,
+    uint32_t offset_alignment, uint64_t* offsets_out, uint64_t* sizes_out, charls_amd_codec_params* params_out,
+    charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_transcode_batch_host(
+    uint32_t frame_count, const void* packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
+    const charls_amd_transcode_spec* specs, uint32_t spec_count, void* packed_out, size_t packed_capacity_bytes,
+    uint32_t offset_alignment, uint64_t* offsets_out, uint64_t* sizes_out, charls_amd_codec_params* params_out,
+    charls_jpegls_errc* errcs);
+CHARLS_AMD_API int32_t charls_amd_transcode_counters(uint64_t* out, int32_t capacity);
+
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */
 CHARLS_AMD_API charls_jpegls_errc charls_amd_set_encode_engine(int32_t engine);
