@@ -157,6 +157,20 @@ def _bind(lib):
         l.charls_amd_transcode_batch_host.restype = C.c_int32
         l.charls_amd_transcode_counters.argtypes = [u64p, C.c_int32]
         l.charls_amd_transcode_counters.restype = C.c_int32
+    if hasattr(l, "charls_amd_encode_batch_device_ragged_budget"):  # (part 2k; an A/B tool may load a build from before it)
+        spec_p = C.POINTER(capi.TranscodeSpec)
+        l.charls_amd_measure_batch_device_ragged.argtypes = [C.c_uint32, C.POINTER(FrameSource), i32p, C.c_uint32, u64p, i32p, C.c_void_p]
+        l.charls_amd_measure_batch_device_ragged.restype = C.c_int32
+        l.charls_amd_encode_batch_device_ragged_budget.argtypes = [C.c_uint32, C.POINTER(FrameSource), u64p, i32p, C.c_uint32, C.c_void_p,
+                                                                   C.c_size_t, C.c_uint32, u64p, u64p, i32p, i32p, C.c_void_p]
+        l.charls_amd_encode_batch_device_ragged_budget.restype = C.c_int32
+        l.charls_amd_transcode_batch_device_budget.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, spec_p, C.c_uint32, u64p, i32p, C.c_uint32,
+                                                               C.c_void_p, C.c_size_t, C.c_uint32, u64p, u64p, i32p, C.POINTER(CodecParams),
+                                                               i32p, C.c_void_p]
+        l.charls_amd_transcode_batch_device_budget.restype = C.c_int32
+        l.charls_amd_transcode_batch_host_budget.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, spec_p, C.c_uint32, u64p, i32p, C.c_uint32,
+                                                             C.c_void_p, C.c_size_t, C.c_uint32, u64p, u64p, i32p, C.POINTER(CodecParams), i32p]
+        l.charls_amd_transcode_batch_host_budget.restype = C.c_int32
     l._batch_bound = True
     return l
 
@@ -1021,6 +1035,110 @@ def encode_batch_budget(frames, budgets, near_candidates, packed, *, alignment=1
     if rc != 0:
         raise capi.JpegLSError(rc, "charls_amd_encode_batch_device_budget")
     return PackedBatch(packed, offsets, sizes, errcs), chosen
+
+
+# ---- byte budgets for ragged frames and for re-coding (charls_amd.h part 2k) ------------------------------------------------
+
+def _frame_sources(frames, params, strides):
+    count = len(frames)
+    if isinstance(params, CodecParams):
+        params = [params] * count
+    assert len(params) == count
+    sources = (FrameSource * max(count, 1))()
+    for f, t in enumerate(frames):
+        assert t.is_cuda
+        stride = strides[f] if strides is not None else _row_stride(t, params[f].interleave_mode == 0)
+        sources[f] = FrameSource(params[f], t.data_ptr(), int(stride), 0, 0)
+    return sources, count
+
+
+def measure_batch_ragged(frames, params, near_candidates, *, strides=None, lib=None):
+    """charls_amd_measure_batch_device_ragged: (sizes, errcs) -- sizes[f, c] = the bytes of frame f's complete .jls at NEAR
+    near_candidates[c], frames and params as for encode_batch_ragged (near_lossless is not looked at); errcs[f] is the code
+    measure_batch raises for a batch of this one frame, its row zeroed then."""
+    import torch
+    l = _bind(lib or capi.load_product())
+    sources, count = _frame_sources(frames, params, strides)
+    nears = np.ascontiguousarray(near_candidates, dtype=np.int32)
+    sizes = np.zeros((count, len(nears)), dtype=np.uint64)
+    errcs = np.zeros(count, dtype=np.int32)
+    stream = torch.cuda.current_stream(frames[0].device).cuda_stream if count else 0
+    rc = l.charls_amd_measure_batch_device_ragged(count, sources, nears.ctypes.data_as(C.POINTER(C.c_int32)), len(nears),
+                                                  sizes.ctypes.data_as(C.POINTER(C.c_uint64)), errcs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_measure_batch_device_ragged")
+    return sizes, errcs
+
+
+def encode_batch_ragged_budget(frames, params, budgets, near_candidates, packed, *, alignment=1, strides=None, capacity=None, lib=None):
+    """charls_amd_encode_batch_device_ragged_budget: encode_batch_ragged with every frame coded at the first NEAR of
+    near_candidates whose complete stream has at most budgets[f] bytes.  Returns (PackedBatch, nears) as encode_batch_budget
+    does; a frame whose parameters the encoder refuses with any candidate has that code in errcs[f]."""
+    import torch
+    l = _bind(lib or capi.load_product())
+    assert packed.is_cuda and packed.is_contiguous()
+    sources, count = _frame_sources(frames, params, strides)
+    nears = np.ascontiguousarray(near_candidates, dtype=np.int32)
+    budgets = np.ascontiguousarray(budgets, dtype=np.uint64)
+    assert len(budgets) == count
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    sizes = np.zeros(count, dtype=np.uint64)
+    chosen = np.zeros(count, dtype=np.int32)
+    errcs = np.zeros(count, dtype=np.int32)
+    stream = torch.cuda.current_stream(packed.device).cuda_stream
+    u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    rc = l.charls_amd_encode_batch_device_ragged_budget(count, sources, budgets.ctypes.data_as(u64p), nears.ctypes.data_as(i32p), len(nears),
+                                                        packed.data_ptr(), packed.numel() if capacity is None else int(capacity), alignment,
+                                                        offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p), chosen.ctypes.data_as(i32p),
+                                                        errcs.ctypes.data_as(i32p), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_encode_batch_device_ragged_budget")
+    return PackedBatch(packed, offsets, sizes, errcs), chosen
+
+
+def _transcode_budget(call, name, blob_in, offsets, sizes, specs, budgets, near_candidates, packed_out, blob_out, nbytes, alignment, capacity,
+                      tail):
+    offsets, sizes, count, table, spec_count = _transcode_tables(offsets, sizes, specs)
+    nears = np.ascontiguousarray(near_candidates, dtype=np.int32)
+    budgets = np.ascontiguousarray(budgets, dtype=np.uint64)
+    assert len(budgets) == count
+    offsets_out = np.zeros(count + 1, dtype=np.uint64)
+    sizes_out = np.zeros(count, dtype=np.uint64)
+    chosen = np.zeros(count, dtype=np.int32)
+    errcs = np.zeros(count, dtype=np.int32)
+    params = (CodecParams * max(count, 1))()
+    u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    rc = call(count, blob_in, offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p), table, spec_count, budgets.ctypes.data_as(u64p),
+              nears.ctypes.data_as(i32p), len(nears), blob_out, nbytes if capacity is None else int(capacity), alignment,
+              offsets_out.ctypes.data_as(u64p), sizes_out.ctypes.data_as(u64p), chosen.ctypes.data_as(i32p), params,
+              errcs.ctypes.data_as(i32p), *tail)
+    if rc != 0:
+        raise capi.JpegLSError(rc, name)
+    return TranscodedBatch(packed_out, offsets_out, sizes_out, errcs, params), chosen
+
+
+def transcode_batch_budget(packed_in, offsets, sizes, specs, budgets, near_candidates, packed_out, *, alignment=1, capacity=None, lib=None):
+    """charls_amd_transcode_batch_device_budget: transcode_batch with every frame re-coded at the first NEAR of near_candidates
+    -- relative to the DECODED pixels -- whose complete stream has at most budgets[f] bytes; specs must not set NEAR.  Returns
+    (TranscodedBatch, nears); nears[f] = -1 for a frame that was not coded."""
+    import torch
+    l = _bind(lib or capi.load_product())
+    assert packed_in.is_cuda and packed_in.is_contiguous() and packed_out.is_cuda and packed_out.is_contiguous()
+    stream = torch.cuda.current_stream(packed_in.device).cuda_stream
+    return _transcode_budget(l.charls_amd_transcode_batch_device_budget, "charls_amd_transcode_batch_device_budget", packed_in.data_ptr(),
+                             offsets, sizes, specs, budgets, near_candidates, packed_out, packed_out.data_ptr(), packed_out.numel(), alignment,
+                             capacity, (C.c_void_p(stream),))
+
+
+def transcode_batch_host_budget(packed_in, offsets, sizes, specs, budgets, near_candidates, packed_out, *, alignment=1, capacity=None, lib=None):
+    """charls_amd_transcode_batch_host_budget: transcode_batch_budget with both blobs in HOST memory (numpy arrays or CPU
+    tensors, pinned or pageable)."""
+    l = _bind(lib or capi.load_product())
+    to, nbytes = _host_contiguous(packed_out)
+    return _transcode_budget(l.charls_amd_transcode_batch_host_budget, "charls_amd_transcode_batch_host_budget",
+                             _host_contiguous(packed_in)[0], offsets, sizes, specs, budgets, near_candidates, packed_out, to, nbytes, alignment,
+                             capacity, ())
 
 
 def measure_counters(lib=None):

@@ -520,7 +520,8 @@ def index_counters(lib: CharLSLibrary | None = None) -> dict:
 
 def transcode_counters(lib: CharLSLibrary | None = None) -> tuple:
     """charls_amd_transcode_counters: (frames re-coded, windows, frames refused for a mapping table, frames behind the one that
-    met the capacity), process-wide since the library was loaded.  The calls themselves: batch.transcode_batch / _host."""
+    met the capacity), process-wide since the library was loaded.  The calls themselves: batch.transcode_batch / _host and, to a
+    byte budget (part 2k), batch.transcode_batch_budget / _host_budget."""
     L = (lib or load_product()).lib
     L.charls_amd_transcode_counters.argtypes = [C.POINTER(C.c_uint64), C.c_int32]
     L.charls_amd_transcode_counters.restype = C.c_int32

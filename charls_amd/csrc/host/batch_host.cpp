@@ -759,9 +759,12 @@ void decode_host_ragged(uint32_t frame_count, const void* packed, const uint64_t
 // charls_amd_transcode_batch_host (charls_amd.h part 2j): the windows one after another on ONE lane -- streams up, the device
 // call's body (batch_transcode.cpp: transcode_frames) on the device window, the front of its blob down.  Nothing runs under
 // anything: a window's copies are two streams per frame, its decode is a dependency chain per frame.
+// charls_amd_transcode_batch_host_budget (part 2k) hands over `budgets`, the candidates and `near_out`, which go to the device
+// call's body window by window as its budgeted encode step; budgets == nullptr is the plain re-code.
 void transcode_host(uint32_t frame_count, const void* packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
-                    const charls_amd_transcode_spec* specs, uint32_t spec_count, void* packed_out, size_t capacity, uint32_t alignment,
-                    uint64_t* offsets_out, uint64_t* sizes_out, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs)
+                    const charls_amd_transcode_spec* specs, uint32_t spec_count, const uint64_t* budgets, const int32_t* near_candidates,
+                    uint32_t candidate_count, void* packed_out, size_t capacity, uint32_t alignment, uint64_t* offsets_out,
+                    uint64_t* sizes_out, int32_t* near_out, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs)
 {
     // ---- the headers, where the bytes are: what every frame will be coded with, the room its stream may take in the device
     // window, and what the device call needs for it in its own areas
@@ -782,8 +785,12 @@ void transcode_host(uint32_t frame_count, const void* packed_in, const uint64_t*
                 const size_t bytes = checked_mul(checked_mul(checked_mul(static_cast<size_t>(fi.component_count), fi.height), fi.width),
                                                  bytes_per_sample(fi.bits_per_sample));
                 coded_with[f] = transcode_params(params_of(reader), specs[spec_count == 1 ? 0 : f]);
-                slot[f] = hs::round_up(estimated_stream_bytes(coded_with[f]), alignment);
-                largest = std::max<uint64_t>(largest, std::max<uint64_t>(slot[f], bytes));
+                // The room of the frame's stream in the window's blob.  Plain re-code: the encoder's slot, which no stream it
+                // writes exceeds.  Budgeted: the staging follows the MEASURED stream, which may be longer than that estimate
+                // (noise coded losslessly) but never than the budget nor than the longest stream the code can produce.
+                const uint64_t estimate = estimated_stream_bytes(coded_with[f]);
+                slot[f] = hs::round_up(budgets != nullptr ? std::min<uint64_t>(budgets[f], longest_stream_bytes(coded_with[f])) : estimate, alignment);
+                largest = std::max<uint64_t>(largest, std::max<uint64_t>(estimate, bytes));
             }
         }
         catch (const error&)
@@ -846,7 +853,10 @@ void transcode_host(uint32_t frame_count, const void* packed_in, const uint64_t*
         const uint64_t room = std::min<uint64_t>(out_bytes, capacity - std::min<uint64_t>(carry.at, capacity));
         const uint32_t beyond = transcode_frames(n, d_in, w_offsets_in.data(), sizes_in + first, specs + (spec_count == 1 ? 0 : first),
                                                  spec_count == 1 ? 1 : n, d_out, static_cast<size_t>(room), alignment, w_offsets_out.data(),
-                                                 sizes_out + first, params_out + first, errcs + first, lane.stream);
+                                                 sizes_out + first, params_out + first, errcs + first,
+                                                 budgets != nullptr ? transcode_encode_budget(budgets + first, near_candidates, candidate_count, near_out + first)
+                                                                    : transcode_encode_plain(),
+                                                 lane.stream);
         for (uint32_t k = 0; k < n; ++k)
             offsets_out[first + k] = carry.at + w_offsets_out[k];
         const size_t front = static_cast<size_t>(std::min<uint64_t>(w_offsets_out[n], room)); // (the zeros behind the last frame stop at the capacity)
@@ -1157,8 +1167,34 @@ try
         return CHARLS_JPEGLS_ERRC_SUCCESS;
     }
     dev::require_device();
-    transcode_host(frame_count, packed_in, offsets_in, sizes_in, specs, spec_count, packed_out, packed_capacity_bytes, offset_alignment,
-                   offsets_out, sizes_out, params_out, errcs);
+    transcode_host(frame_count, packed_in, offsets_in, sizes_in, specs, spec_count, nullptr, nullptr, 0, packed_out, packed_capacity_bytes,
+                   offset_alignment, offsets_out, sizes_out, nullptr, params_out, errcs);
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}
+
+// ---- part 2k on host blobs
+extern "C" charls_jpegls_errc charls_amd_transcode_batch_host_budget(
+    uint32_t frame_count, const void* packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in, const charls_amd_transcode_spec* specs,
+    uint32_t spec_count, const uint64_t* budgets, const int32_t* near_candidates, uint32_t candidate_count, void* packed_out,
+    size_t packed_capacity_bytes, uint32_t offset_alignment, uint64_t* offsets_out, uint64_t* sizes_out, int32_t* near_out,
+    charls_amd_codec_params* params_out, charls_jpegls_errc* errcs)
+try
+{
+    check_transcode_budget_call(frame_count, packed_in, offsets_in, sizes_in, specs, spec_count, budgets, near_candidates, candidate_count,
+                                packed_out, offset_alignment, offsets_out, sizes_out, near_out, params_out, errcs);
+    if (frame_count == 0)
+    {
+        offsets_out[0] = 0;
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    }
+    dev::require_device();
+    transcode_host(frame_count, packed_in, offsets_in, sizes_in, specs, spec_count, budgets, near_candidates, candidate_count, packed_out,
+                   packed_capacity_bytes, offset_alignment, offsets_out, sizes_out, near_out, params_out, errcs);
+    transcode_near_of_uncoded(frame_count, errcs, near_out);
     return CHARLS_JPEGLS_ERRC_SUCCESS;
 }
 catch (...)

@@ -38,6 +38,21 @@ size_t jls::estimated_stream_bytes(const charls_amd_codec_params& p)
     return size + extra;
 }
 
+size_t jls::longest_stream_bytes(const charls_amd_codec_params& p)
+{
+    const charls_frame_info& f = p.frame_info;
+    const size_t rest = estimated_stream_bytes(p); // (the container, the markers and padding of restart intervals: its `extra`)
+    if (rest == 1)
+        return 1;
+    // A regular sample is a Golomb code of at most LIMIT = 2 * (bpp + max(8, bpp)) bits; a run costs at most a bit per sample,
+    // and the sample that ends it 1 + J bits of run length and at most LIMIT - J - 1 of error.  After a 0xFF byte the next
+    // holds seven bits: at most 8 / 7 of the bytes.
+    const size_t bpp = static_cast<size_t>(std::max<int32_t>(f.bits_per_sample, 2));
+    const size_t limit_bits = 2 * (bpp + std::max<size_t>(8, bpp));
+    const size_t samples = static_cast<size_t>(f.width) * f.height * static_cast<size_t>(f.component_count);
+    return checked_mul(samples, limit_bits) / 7 + rest;
+}
+
 extern "C" charls_jpegls_errc charls_amd_pack_streams_device(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
                                                              const uint64_t* sizes, void* d_packed, size_t packed_capacity_bytes,
                                                              uint32_t offset_alignment, uint64_t* offsets, void* hip_stream)

@@ -3,6 +3,7 @@
 // (batch_api.cpp, batch_index.cpp), the event-pair timer event_timer.h.
 #pragma once
 #include <cstdint>
+#include <functional>
 
 #include "../device/scan_types.h"
 #include "common.h"
@@ -70,6 +71,17 @@ void encode_batch_frames(const charls_amd_codec_params& params, uint32_t frame_c
 // destination_too_small --, or frame_count.
 uint32_t encode_ragged_frames(uint32_t frame_count, const charls_amd_frame_source* sources, void* d_packed, size_t packed_capacity_bytes,
                               uint32_t offset_alignment, uint64_t* offsets, uint64_t* sizes, charls_jpegls_errc* errcs, void* hip_stream);
+// The body of charls_amd_encode_batch_device_ragged_budget (batch_budget.cpp; charls_amd.h part 2k) behind its whole-call checks,
+// factored as encode_ragged_frames is: the frames are sized group by group, every frame's first candidate within budgets[f] is
+// picked, and the picked (frame, NEAR) pairs go through ONE encode_ragged_frames.  sources[f].params.near_lossless and
+// .max_stream_bytes are not looked at.  Returns the first frame beyond the capacity, or frame_count.  The caller's tables are
+// written only when nothing was raised.
+uint32_t encode_ragged_budget_frames(uint32_t frame_count, const charls_amd_frame_source* sources, const uint64_t* budgets,
+                                     const int32_t* near_candidates, uint32_t candidate_count, void* d_packed, size_t packed_capacity_bytes,
+                                     uint32_t offset_alignment, uint64_t* offsets, uint64_t* sizes, int32_t* near_out,
+                                     charls_jpegls_errc* errcs, void* hip_stream);
+// The whole-call checks on what the budget calls of part 2k take beyond the calls they extend; needs no device.
+void check_budget_tables(const uint64_t* budgets, const int32_t* near_candidates, uint32_t candidate_count, const int32_t* near_out);
 // Raises what the batch encoder raises for these parameters before it codes anything (needs no GPU).
 void check_encode_params(const charls_amd_codec_params& params, size_t frame_bytes, uint32_t stride_arg);
 
@@ -85,12 +97,27 @@ EncodePlan plan_encode(const charls_amd_codec_params& params, size_t frame_bytes
 
 // charls_jpegls_encoder_get_estimated_destination_size for the frames of `p` (batch_packed.cpp).
 size_t estimated_stream_bytes(const charls_amd_codec_params& p);
+// An upper bound on the complete .jls the batch encoder can write for the frames of `p` at any NEAR, whatever they hold
+// (batch_packed.cpp): no sample takes more than LIMIT bits of ISO 14495-1, in either mode, and stuffing adds at most a bit per
+// seven.  What estimated_stream_bytes returns is not such a bound: noise coded losslessly is a little longer.
+size_t longest_stream_bytes(const charls_amd_codec_params& p);
 
 // charls_amd_transcode_batch_device (batch_transcode.cpp; charls_amd.h part 2j) in three pieces, which the host form
 // (batch_host.cpp) uses too: `p` with the fields that spec.set names replaced; the whole-call checks, which raise before a
 // device is asked for (the blobs are DEVICE pointers in one form and HOST pointers in the other: only looked at for NULL);
 // and the body behind them -- frame_count >= 1, a device is there --, which returns the first frame, in the caller's order,
 // whose end lay beyond packed_capacity_bytes, or frame_count.
+//
+// The ENCODE STEP of a window is a parameter of the body: it codes the `count` frames `sources` that decoded -- frames
+// sent[0 .. count) of the call, in its order, with the spec applied and max_stream_bytes 0 -- to d_packed under the contract of
+// encode_ragged_frames, whose arguments and return value the rest are, and leaves in sources[k].params what frame k was coded
+// with.  transcode_encode_plain is encode_ragged_frames itself (part 2j); transcode_encode_budget (batch_budget.cpp, part 2k)
+// is encode_ragged_budget_frames with budgets[sent[k]], and sets near_out[sent[k]] (-1 for a frame that was not coded).
+using TranscodeEncode = std::function<uint32_t(uint32_t count, charls_amd_frame_source* sources, const uint32_t* sent, void* d_packed,
+                                               size_t packed_capacity_bytes, uint32_t offset_alignment, uint64_t* offsets, uint64_t* sizes,
+                                               charls_jpegls_errc* errcs, void* hip_stream)>;
+TranscodeEncode transcode_encode_plain();
+TranscodeEncode transcode_encode_budget(const uint64_t* budgets, const int32_t* near_candidates, uint32_t candidate_count, int32_t* near_out);
 charls_amd_codec_params transcode_params(charls_amd_codec_params p, const charls_amd_transcode_spec& spec) noexcept;
 void check_transcode_call(uint32_t frame_count, const void* packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
                           const charls_amd_transcode_spec* specs, uint32_t spec_count, const void* packed_out, uint32_t offset_alignment,
@@ -99,7 +126,15 @@ void check_transcode_call(uint32_t frame_count, const void* packed_in, const uin
 uint32_t transcode_frames(uint32_t frame_count, const void* d_packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
                           const charls_amd_transcode_spec* specs, uint32_t spec_count, void* d_packed_out, size_t packed_capacity_bytes,
                           uint32_t offset_alignment, uint64_t* offsets_out, uint64_t* sizes_out, charls_amd_codec_params* params_out,
-                          charls_jpegls_errc* errcs, void* hip_stream);
+                          charls_jpegls_errc* errcs, const TranscodeEncode& encode, void* hip_stream);
+// Part 2k, both forms: check_transcode_call plus the budget tables, the candidate count and a spec that sets NEAR (the
+// candidates decide it); and, behind the body, near_out[f] = -1 for every frame that was not coded (errcs[f] is not success).
+void check_transcode_budget_call(uint32_t frame_count, const void* packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
+                                 const charls_amd_transcode_spec* specs, uint32_t spec_count, const uint64_t* budgets,
+                                 const int32_t* near_candidates, uint32_t candidate_count, const void* packed_out, uint32_t offset_alignment,
+                                 const uint64_t* offsets_out, const uint64_t* sizes_out, const int32_t* near_out,
+                                 const charls_amd_codec_params* params_out, const charls_jpegls_errc* errcs);
+void transcode_near_of_uncoded(uint32_t frame_count, const charls_jpegls_errc* errcs, int32_t* near_out) noexcept;
 void transcode_count_behind_capacity(uint64_t frames) noexcept; // charls_amd_transcode_counters [3], for windows the host form does not send
 
 // What the lanes of the host-memory calls (batch_host.cpp; charls_amd.h part 2i) hold, device and pinned, given back: the

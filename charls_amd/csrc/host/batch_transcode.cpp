@@ -9,6 +9,9 @@
 //    d_packed_out + base, base being the end of the window before it -- a multiple of the alignment, so that bytes, gaps and
 //    offsets are those of one encode over all frames.
 //  * charls_amd_transcode_batch_host (batch_host.cpp) runs the same body on device windows of host blobs.
+//  * The ENCODE STEP of a window is a parameter of the body (batch_streams.h: TranscodeEncode): the ragged encode here, the
+//    budgeted one (batch_budget.cpp: NEAR picked per frame from a list of candidates) in charls_amd_transcode_batch_device_budget
+//    and its host form (charls_amd.h part 2k).  Everything else -- probe, windows, decode, offsets, capacity tail -- is shared.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +48,14 @@ void count(Counter c, uint64_t n) noexcept
 }
 
 } // namespace
+
+TranscodeEncode jls::transcode_encode_plain()
+{
+    return [](uint32_t count, charls_amd_frame_source* sources, const uint32_t*, void* d_packed, size_t packed_capacity_bytes,
+              uint32_t offset_alignment, uint64_t* offsets, uint64_t* sizes, charls_jpegls_errc* errcs, void* hip_stream) {
+        return encode_ragged_frames(count, sources, d_packed, packed_capacity_bytes, offset_alignment, offsets, sizes, errcs, hip_stream);
+    };
+}
 
 void jls::transcode_count_behind_capacity(uint64_t frames) noexcept
 {
@@ -92,10 +103,32 @@ void jls::check_transcode_call(uint32_t frame_count, const void* packed_in, cons
     }
 }
 
+void jls::check_transcode_budget_call(uint32_t frame_count, const void* packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
+                                      const charls_amd_transcode_spec* specs, uint32_t spec_count, const uint64_t* budgets,
+                                      const int32_t* near_candidates, uint32_t candidate_count, const void* packed_out,
+                                      uint32_t offset_alignment, const uint64_t* offsets_out, const uint64_t* sizes_out,
+                                      const int32_t* near_out, const charls_amd_codec_params* params_out, const charls_jpegls_errc* errcs)
+{
+    check_budget_tables(budgets, near_candidates, candidate_count, near_out);
+    check_pointer(specs);
+    check_argument(spec_count == 1 || spec_count == frame_count);
+    for (uint32_t k = 0; k < spec_count; ++k) // (the candidates decide NEAR)
+        check_argument((specs[k].set & CHARLS_AMD_TRANSCODE_NEAR) == 0);
+    check_transcode_call(frame_count, packed_in, offsets_in, sizes_in, specs, spec_count, packed_out, offset_alignment, offsets_out, sizes_out,
+                         params_out, errcs);
+}
+
+void jls::transcode_near_of_uncoded(uint32_t frame_count, const charls_jpegls_errc* errcs, int32_t* near_out) noexcept
+{
+    for (uint32_t f = 0; f < frame_count; ++f)
+        if (errcs[f] != CHARLS_JPEGLS_ERRC_SUCCESS)
+            near_out[f] = -1;
+}
+
 uint32_t jls::transcode_frames(uint32_t frame_count, const void* d_packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
                                const charls_amd_transcode_spec* specs, uint32_t spec_count, void* d_packed_out, size_t packed_capacity_bytes,
                                uint32_t offset_alignment, uint64_t* offsets_out, uint64_t* sizes_out, charls_amd_codec_params* params_out,
-                               charls_jpegls_errc* errcs, void* hip_stream)
+                               charls_jpegls_errc* errcs, const TranscodeEncode& encode, void* hip_stream)
 {
     auto spec_of = [&](uint32_t f) -> const charls_amd_transcode_spec& { return specs[spec_count == 1 ? 0 : f]; };
 
@@ -191,7 +224,7 @@ uint32_t jls::transcode_frames(uint32_t frame_count, const void* d_packed_in, co
         decode_ms += t.count > 0 ? t.values[0] : 0;
         scan_ms += t.count > 1 ? t.values[1] : 0;
 
-        // ---- 2. the ragged encode of the frames that decoded, behind the window before
+        // ---- 2. the encode step on the frames that decoded, behind the window before
         sent.clear();
         sources.clear();
         for (uint32_t k = 0; k < n; ++k)
@@ -220,8 +253,8 @@ uint32_t jls::transcode_frames(uint32_t frame_count, const void* d_packed_in, co
             c_sizes.assign(m, 0);
             c_errcs.assign(m, CHARLS_JPEGLS_ERRC_SUCCESS);
             const uint64_t reach = std::min<uint64_t>(base, packed_capacity_bytes);
-            beyond = encode_ragged_frames(m, sources.data(), out + reach, packed_capacity_bytes - static_cast<size_t>(reach), offset_alignment,
-                                          c_offsets.data(), c_sizes.data(), c_errcs.data(), hip_stream);
+            beyond = encode(m, sources.data(), sent.data(), out + reach, packed_capacity_bytes - static_cast<size_t>(reach), offset_alignment,
+                            c_offsets.data(), c_sizes.data(), c_errcs.data(), hip_stream);
             const dev::Timings& e = dev::last_timings();
             encode_ms += e.count > 0 ? e.values[0] : 0;
             scan_ms += e.count > 1 ? e.values[1] : 0;
@@ -235,6 +268,7 @@ uint32_t jls::transcode_frames(uint32_t frame_count, const void* d_packed_in, co
             {
                 sizes_out[f] = c_sizes[c];
                 errcs[f] = c_errcs[c];
+                params_out[f] = sources[c].params; // (what the step coded it with: the candidate it picked, in the budgeted form)
                 ++c;
             }
         }
@@ -260,7 +294,7 @@ uint32_t jls::transcode_frames(uint32_t frame_count, const void* d_packed_in, co
     for (uint32_t f = 0; f < frame_count; ++f)
         recoded += errcs[f] == CHARLS_JPEGLS_ERRC_SUCCESS ? 1 : 0;
     count(kRecoded, recoded);
-    dev::Timings& t = dev::last_timings(); // charls_amd_last_timings: [0] all launches, [1] the dominant kernels, [2] decoding, [3] encoding
+    dev::Timings& t = dev::last_timings(); // charls_amd_last_timings: [0] all launches, [1] the dominant kernels, [2] decoding, [3] the encode steps (sizing and encoding)
     t.values[0] = decode_ms + encode_ms;
     t.values[1] = scan_ms;
     t.values[2] = decode_ms;
@@ -285,7 +319,34 @@ try
     }
     dev::require_device();
     transcode_frames(frame_count, d_packed_in, offsets_in, sizes_in, specs, spec_count, d_packed_out, packed_capacity_bytes, offset_alignment,
-                     offsets_out, sizes_out, params_out, errcs, hip_stream);
+                     offsets_out, sizes_out, params_out, errcs, transcode_encode_plain(), hip_stream);
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}
+
+// Part 2k: the same body with the budgeted encode step.
+extern "C" charls_jpegls_errc charls_amd_transcode_batch_device_budget(
+    uint32_t frame_count, const void* d_packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
+    const charls_amd_transcode_spec* specs, uint32_t spec_count, const uint64_t* budgets, const int32_t* near_candidates,
+    uint32_t candidate_count, void* d_packed_out, size_t packed_capacity_bytes, uint32_t offset_alignment, uint64_t* offsets_out,
+    uint64_t* sizes_out, int32_t* near_out, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs, void* hip_stream)
+try
+{
+    check_transcode_budget_call(frame_count, d_packed_in, offsets_in, sizes_in, specs, spec_count, budgets, near_candidates, candidate_count,
+                                d_packed_out, offset_alignment, offsets_out, sizes_out, near_out, params_out, errcs);
+    if (frame_count == 0)
+    {
+        offsets_out[0] = 0;
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    }
+    dev::require_device();
+    transcode_frames(frame_count, d_packed_in, offsets_in, sizes_in, specs, spec_count, d_packed_out, packed_capacity_bytes, offset_alignment,
+                     offsets_out, sizes_out, params_out, errcs, transcode_encode_budget(budgets, near_candidates, candidate_count, near_out),
+                     hip_stream);
+    transcode_near_of_uncoded(frame_count, errcs, near_out);
     return CHARLS_JPEGLS_ERRC_SUCCESS;
 }
 catch (...)

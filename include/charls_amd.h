@@ -642,7 +642,8 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_encode_batch_device_ragged(uint32_t
  * it has been coded.  These calls walk the coding chains of every frame at every candidate NEAR in one launch that writes no
  * stream (K candidates of N frames cost K x N x scans results of 16 bytes, no stream slots), report the sizes, and code
  * every frame once, at the first candidate its budget allows.  Frames are uniform as in part 2 (frame f at d_frames +
- * f * frame_pitch_bytes, one params, one stride); params->near_lossless is not looked at.  `near_candidates`, `budgets`,
+ * f * frame_pitch_bytes, one params, one stride; not done here: ragged frames and streams as the source, which are part 2k);
+ * params->near_lossless is not looked at.  `near_candidates`, `budgets`,
  * `sizes_out`, `offsets`, `sizes`, `near_out` and `errcs` are HOST arrays; candidate_count is 1 .. 64; the candidates may
  * come in any order and may repeat: the order given is the order of preference.
  *
@@ -943,8 +944,8 @@ CHARLS_AMD_API int32_t charls_amd_host_counters(uint64_t* out, int32_t capacity)
  *   call, out[2] frames refused for a mapping table, out[3] frames behind the one that met the capacity.  Returns the number
  *   of values written (4 at most).
  * Not done: the decode of window w + 1 does not run under the encode of window w (the group decoder takes 156 of a CU's
- *   160 KB of LDS: the tile kernels cannot sit beside it); the interleave mode cannot be changed; the byte budget of part 2f
- *   and the multi-device calls of part 2b are not joined to it.
+ *   160 KB of LDS: the tile kernels cannot sit beside it); the interleave mode cannot be changed; the multi-device calls of
+ *   part 2b are not joined to it.  The byte budget of part 2f is joined to it in part 2k.
  * ---------------------------------------------------------------------------------------------------------------- */
 #define CHARLS_AMD_TRANSCODE_NEAR 1u
 #define CHARLS_AMD_TRANSCODE_RESTART_INTERVAL 2u
@@ -971,6 +972,92 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_transcode_batch_host(
     uint32_t offset_alignment, uint64_t* offsets_out, uint64_t* sizes_out, charls_amd_codec_params* params_out,
     charls_jpegls_errc* errcs);
 CHARLS_AMD_API int32_t charls_amd_transcode_counters(uint64_t* out, int32_t capacity);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Part 2k -- BYTE BUDGETS for ragged frames and for re-coding: part 2f joined with part 2e and with part 2j.  "Every frame of
+ * this archive at no more than N bytes" is one call; the caller neither sorts frames into geometry groups nor owns decoded
+ * frames.  All tables are HOST arrays as in parts 2e, 2f and 2j; `offsets` / `offsets_out` have frame_count + 1 elements,
+ * `sizes_out` of the measure call frame_count * candidate_count.  The candidates are ONE list for the whole call, 1 .. 64
+ * entries in any order, possibly repeating; the order given is the order of preference.  New entry points beside the existing
+ * ones, none of which changes; no kernel, instantiation or descriptor field was added for them.
+ *
+ * measure_batch_device_ragged: row f of sizes_out is what charls_amd_measure_batch_device reports for a batch that holds this
+ *   one frame, with sources[f].params, .stride and .d_pixels; params.near_lossless is not looked at.  Where that call would
+ *   refuse the frame as a whole call -- a candidate above the frame's largest legal NEAR, NEAR > 0 with a colour
+ *   transformation, preset parameters invalid at some candidate, a stride below the row -- its return value is errcs[f] and the
+ *   row is zeroed; no other frame is affected.
+ * encode_batch_device_ragged_budget: frame f gets exactly the near_out, sizes, errcs and stream bytes that
+ *   charls_amd_encode_batch_device_budget gives a batch holding this one frame with budgets[f], placed by the offset rule of
+ *   part 2d in the caller's frame order with zeroed gaps.  No candidate fits: destination_too_small, near_out[f] == -1,
+ *   sizes[f] == 0, no room taken.  Parameters the encoder refuses with ANY candidate: that code, with -1, 0 and no room, as in
+ *   the measure call.  The capacity rule of part 2d: the frame whose end lies beyond packed_capacity_bytes is
+ *   destination_too_small (near_out -1), so is every frame behind it in the caller's order, and nothing is written at or
+ *   beyond the capacity.  The same pixels may be named by several frames, for example with different budgets.
+ * transcode_batch_device_budget: a composition, as part 2j is.  Frame f's output is what encode_batch_device_ragged_budget
+ *   writes for one source whose pixels are what charls_amd_decode_batch_device_ragged decodes from input stream f into a packed
+ *   destination, whose params are that decode's params_out[f] with the fields named by specs[f].set replaced, and whose budget
+ *   is budgets[f].  params_out[f] is what the frame was coded with: near_lossless == near_out[f].  For a frame that was not
+ *   coded, near_out[f] == -1 and params_out[f] is the source's parameters with the spec applied where the header could be
+ *   read, zeroed otherwise (the rule of part 2j).  A frame whose decode fails, a frame that names a mapping table, the offsets
+ *   and the capacity rule "this frame and every frame behind it" are those of part 2j, unchanged.
+ *   The candidates are relative to the DECODED pixels: re-coding a near-lossless source stacks its NEAR with the chosen one
+ *   (a source of NEAR 2 re-coded at candidate 3 may be off by 5 from what was first coded), and candidate 0 keeps the
+ *   source's loss, it does not undo it.
+ *   The call re-codes EVERY frame it is given.  A caller who wants frames that are already within their budget left alone
+ *   leaves them out of the call: it holds sizes_in.
+ * transcode_batch_host_budget: the same arguments with both blobs in HOST memory and no hip_stream; the results are those of
+ *   the device call on device copies of the same bytes.  It runs in windows on one lane, exactly as
+ *   charls_amd_transcode_batch_host does, budgets and candidates passed through window by window.
+ * Errors of the whole call, all checked before a device is asked for, nothing being written.  invalid_argument: NULL tables
+ *   or blobs, a candidate_count outside 1 .. 64, an offset_alignment that is no power of two in [1, 4096], a `reserved` that
+ *   is not 0, a d_pixels of NULL, a sources[f].max_stream_bytes that is not 0 (the budget is the limit), a spec_count that is
+ *   neither 1 nor frame_count, a `set` bit that is not defined, a spec with CHARLS_AMD_TRANSCODE_NEAR set (the candidates
+ *   decide NEAR).  invalid_argument_size: an offsets_in[f] + sizes_in[f] that overflows.  frame_count == 0 is success with
+ *   offsets[0] == 0.
+ * How: the frames are walked once; frames with equal params (NEAR aside) and equal stride are a GROUP, in any positions of the
+ *   caller's order.  Every group is sized by what one uniform call of part 2f over its frames does -- ONE measuring launch
+ *   for all its frames and candidates, and the same fallback of coding for real for scans the group encoder does not take
+ *   and for restart intervals --, never one call per frame.  The chosen (frame, NEAR) pairs of the whole call -- of the whole
+ *   window when re-coding -- go through one ragged encode of part 2e, whose staging slots are sized per group and NEAR by
+ *   the largest measured stream, so that the frames of a group that chose the same NEAR stay one encode group.  Re-coding
+ *   shares the probe, the window plan, the decode, the offset arithmetic and the capacity tail with part 2j; only the encode
+ *   step of a window differs.  Work areas are those of parts 2d and 2j under their rules (a quarter of what the thread's work
+ *   areas may hold; not_enough_memory, before anything is written, when a configured workspace limit cannot hold the largest
+ *   frame or its staging slot; TRANSCODE_WINDOW_FRAMES forces the window length).
+ * Counters: sizing launches, sized scans and scans coded for real count into charls_amd_measure_counters; re-coded frames,
+ *   windows, table refusals and frames behind the capacity into charls_amd_transcode_counters.  charls_amd_last_timings after
+ *   a transcode call: [0] all launches, [1] their dominant kernels, [2] the decodes, [3] sizing and encoding, ms.
+ * As in part 2f the staging slots follow the MEASURED streams, not part 1's estimated destination size: a frame whose stream
+ *   is longer than that estimate (noise coded losslessly) is coded here, where charls_amd_encode_batch_device_packed with
+ *   max_stream_bytes = 0 reports destination_too_small for it.  The host form gives every frame of a window the smaller of
+ *   budgets[f] and the longest stream the code can produce for its geometry (LIMIT bits per sample and the stuffing) as room
+ *   in the window's device blob, so such frames are coded there as well; budgets far above the frames' sizes make its windows
+ *   shorter, nothing else.  The not_enough_memory check that comes before anything is written covers the largest frame and
+ *   part 1's estimate of its stream: with a configured workspace limit between that estimate and the staging slot of a
+ *   measured stream that is longer, a later window can return not_enough_memory after earlier windows have written theirs.
+ *   A stride of 0 and a stride that states the packed row are different groups: the frames are coded the same, in one launch
+ *   more.
+ * Not done: one measuring launch over mixed geometries (the ragged encoder has no such launch either: G groups cost G
+ *   launches); copying through, instead of re-coding, frames that are already within budget; the interleave mode; the
+ *   multi-device calls of part 2b; a budgeted encode from host pixels.
+ * ---------------------------------------------------------------------------------------------------------------- */
+CHARLS_AMD_API charls_jpegls_errc charls_amd_measure_batch_device_ragged(
+    uint32_t frame_count, const charls_amd_frame_source* sources, const int32_t* near_candidates, uint32_t candidate_count,
+    uint64_t* sizes_out, charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_encode_batch_device_ragged_budget(
+    uint32_t frame_count, const charls_amd_frame_source* sources, const uint64_t* budgets, const int32_t* near_candidates,
+    uint32_t candidate_count, void* d_packed, size_t packed_capacity_bytes, uint32_t offset_alignment, uint64_t* offsets,
+    uint64_t* sizes, int32_t* near_out, charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_transcode_batch_device_budget(
+    uint32_t frame_count, const void* d_packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
+    const charls_amd_transcode_spec* specs, uint32_t spec_count, const uint64_t* budgets, const int32_t* near_candidates,
+    uint32_t candidate_count, void* d_packed_out, size_t packed_capacity_bytes, uint32_t offset_alignment, uint64_t* offsets_out,
+    uint64_t* sizes_out, int32_t* near_out, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_transcode_batch_host_budget(
+    uint32_t frame_count, const void* packed_in, const uint64_t* offsets_in, const uint64_t* sizes_in,
+    const charls_amd_transcode_spec* specs, uint32_t spec_count, const uint64_t* budgets, const int32_t* near_candidates,
+    uint32_t candidate_count, void* packed_out, size_t packed_capacity_bytes, uint32_t offset_alignment, uint64_t* offsets_out,
+    uint64_t* sizes_out, int32_t* near_out, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs);
 
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */

@@ -96,7 +96,9 @@ assert all(int(result.sizes[f]) <= int(budgets[f]) for f in range(N) if nears[f]
 
 # ---- (c) the same selection with the calls that were there before
 say("(c) the same selection without part 2f: one encode_batch_device per candidate into slots, sizes compared on the host, then ragged")
-slot = (batch.estimated_destination_size(S, S, 8, 1) + 255) & ~255
+# (twice the frame: the lossless stream of a noise frame is a little longer than part 1's estimated destination size, which the
+# budget call does not depend on -- its staging slots are sized by the measured streams)
+slot = (2 * S * S + 4096 + 255) & ~255
 slots = torch.empty((N, slot), dtype=torch.uint8, device="cuda:0")
 packed_c = torch.empty_like(packed)
 
