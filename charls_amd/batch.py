@@ -171,6 +171,19 @@ def _bind(lib):
         l.charls_amd_transcode_batch_host_budget.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, spec_p, C.c_uint32, u64p, i32p, C.c_uint32,
                                                              C.c_void_p, C.c_size_t, C.c_uint32, u64p, u64p, i32p, C.POINTER(CodecParams), i32p]
         l.charls_amd_transcode_batch_host_budget.restype = C.c_int32
+    if hasattr(l, "charls_amd_index_batch_device_packed"):  # (part 2l; an A/B tool may load a build from before it)
+        l.charls_amd_index_batch_device_packed.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.POINTER(FrameDest), C.c_uint32, C.c_void_p,
+                                                           C.c_size_t, u64p, C.POINTER(CodecParams), i32p, C.c_void_p]
+        l.charls_amd_index_batch_device_packed.restype = C.c_int32
+        l.charls_amd_decode_batch_device_ragged_indexed.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.c_void_p, C.c_size_t, u64p,
+                                                                    C.POINTER(FrameDest), C.POINTER(CodecParams), i32p, C.c_void_p]
+        l.charls_amd_decode_batch_device_ragged_indexed.restype = C.c_int32
+        l.charls_amd_decode_rows_batch_device_ragged.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.c_void_p, C.c_size_t, u64p, u32p, u32p,
+                                                                 C.POINTER(FrameDest), i32p, C.c_void_p]
+        l.charls_amd_decode_rows_batch_device_ragged.restype = C.c_int32
+        l.charls_amd_index_batch_host.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.c_uint32, C.c_void_p, C.c_size_t, u64p,
+                                                  C.POINTER(CodecParams), i32p]
+        l.charls_amd_index_batch_host.restype = C.c_int32
     l._batch_bound = True
     return l
 
@@ -1139,6 +1152,133 @@ def transcode_batch_host_budget(packed_in, offsets, sizes, specs, budgets, near_
     return _transcode_budget(l.charls_amd_transcode_batch_host_budget, "charls_amd_transcode_batch_host_budget",
                              _host_contiguous(packed_in)[0], offsets, sizes, specs, budgets, near_candidates, packed_out, to, nbytes, alignment,
                              capacity, ())
+
+
+# ---- the seek-point index on packed streams (charls_amd.h part 2l) ---------------------------------------------------------
+
+def _index_table(count, index_pitch, indexes_out):
+    """The host table the indexes of a build go to: (count, pitch) uint8, the caller's own where it brings one."""
+    if indexes_out is None:
+        return np.zeros((max(count, 1), int(index_pitch)), dtype=np.uint8)
+    assert indexes_out.dtype == np.uint8 and indexes_out.ndim == 2 and indexes_out.flags["C_CONTIGUOUS"]
+    assert indexes_out.shape[0] >= count and indexes_out.shape[1] == int(index_pitch)
+    return indexes_out
+
+
+def index_pitch_of(params, errcs, lines_per_seek_point, *, lib=None) -> int:
+    """The largest charls_amd_index_size_bound of the frames a probe describes (probe_packed / probe_host): an index_pitch
+    that holds every frame's index."""
+    l = _bind(lib or capi.load_product())
+    most = 16
+    for f, e in enumerate(errcs):
+        if e != 0 or params[f].frame_info.width == 0:
+            continue
+        out = C.c_size_t(0)
+        if l.charls_amd_index_size_bound(C.byref(params[f]), lines_per_seek_point, C.byref(out)) == 0:
+            most = max(most, int(out.value))
+    return most
+
+
+def index_batch_packed(packed, offsets, sizes, lines_per_seek_point=64, *, outs=None, strides=None, capacities=None, index_pitch=None,
+                       indexes_out=None, lib=None):
+    """charls_amd_index_batch_device_packed: the seek-point index of every stream of a packed blob.  outs=None is the
+    index-only build (no frame is allocated or written); with outs -- device tensors as decode_batch_ragged takes them --
+    the frames are decoded as well.  index_pitch: bytes kept per index (by default what a probe of the blob says the largest
+    needs); indexes_out: a (frames, index_pitch) uint8 host array of the caller's to build into.
+    Returns (params -- a ctypes array --, errcs, [index bytes]); the index of a frame that failed is b""."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert packed.is_cuda and packed.is_contiguous()
+    offsets, sizes, count = _tables(offsets, sizes)
+    if index_pitch is None:
+        probed, _, probe_errcs = probe_packed(packed, offsets, sizes, lib=lib)
+        index_pitch = index_pitch_of(probed, probe_errcs, lines_per_seek_point, lib=lib)
+    assert outs is None or len(outs) == count
+    dests = _frame_dests(outs, strides, capacities) if outs is not None else None
+    table = _index_table(count, index_pitch, indexes_out)
+    index_sizes = np.zeros(max(count, 1), dtype=np.uint64)
+    params = (CodecParams * max(count, 1))()
+    errcs = np.zeros(count, dtype=np.int32)
+    u64p = C.POINTER(C.c_uint64)
+    stream = torch.cuda.current_stream(packed.device).cuda_stream
+    rc = l.charls_amd_index_batch_device_packed(count, packed.data_ptr(), offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p), dests,
+                                                lines_per_seek_point, table.ctypes.data, int(index_pitch), index_sizes.ctypes.data_as(u64p),
+                                                params, errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_index_batch_device_packed")
+    return params, errcs, [table[f, :int(index_sizes[f])].tobytes() for f in range(count)]
+
+
+def index_batch_host(packed, offsets, sizes, lines_per_seek_point=64, *, index_pitch=None, indexes_out=None, lib=None):
+    """charls_amd_index_batch_host: the index-only build of index_batch_packed with the blob in HOST memory (a numpy array or a
+    CPU tensor, pinned or pageable).  Returns (params, errcs, [index bytes])."""
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    offsets, sizes, count = _tables(offsets, sizes)
+    if index_pitch is None:
+        probed, _, probe_errcs = probe_host(packed, offsets, sizes, lib=lib)
+        index_pitch = index_pitch_of(probed, probe_errcs, lines_per_seek_point, lib=lib)
+    table = _index_table(count, index_pitch, indexes_out)
+    index_sizes = np.zeros(max(count, 1), dtype=np.uint64)
+    params = (CodecParams * max(count, 1))()
+    errcs = np.zeros(count, dtype=np.int32)
+    u64p = C.POINTER(C.c_uint64)
+    rc = l.charls_amd_index_batch_host(count, _host_contiguous(packed)[0], offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p),
+                                       lines_per_seek_point, table.ctypes.data, int(index_pitch), index_sizes.ctypes.data_as(u64p), params,
+                                       errcs.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_index_batch_host")
+    return params, errcs, [table[f, :int(index_sizes[f])].tobytes() for f in range(count)]
+
+
+def decode_batch_ragged_indexed(packed, offsets, sizes, indexes, outs, *, strides=None, capacities=None, lib=None):
+    """charls_amd_decode_batch_device_ragged_indexed: decode_batch_ragged through seek-point indexes (a list of bytes; None or
+    b"" = that frame decodes the ordinary way).  Returns (params -- a ctypes array --, errcs)."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert packed.is_cuda and packed.is_contiguous()
+    offsets, sizes, count = _tables(offsets, sizes)
+    assert len(outs) == count
+    table, pitch, index_sizes = _pack_indexes(indexes, count)
+    dests = _frame_dests(outs, strides, capacities)
+    params = (CodecParams * max(count, 1))()
+    errcs = np.zeros(count, dtype=np.int32)
+    u64p = C.POINTER(C.c_uint64)
+    stream = torch.cuda.current_stream(packed.device).cuda_stream
+    rc = l.charls_amd_decode_batch_device_ragged_indexed(count, packed.data_ptr(), offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p),
+                                                         table.ctypes.data, pitch, index_sizes.ctypes.data_as(u64p), dests, params,
+                                                         errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_decode_batch_device_ragged_indexed")
+    return params, errcs
+
+
+def decode_rows_batch_ragged(packed, offsets, sizes, indexes, first_rows, row_counts, bands, *, strides=None, capacities=None, lib=None):
+    """charls_amd_decode_rows_batch_device_ragged: rows [first_rows[f], first_rows[f] + row_counts[f]) of frame f of the packed
+    streams into bands[f], a device tensor of its own (decode_rows' layout), through the frame's index where indexes[f] is
+    one, from the top otherwise.  Returns errcs."""
+    import torch
+    lib = lib or capi.load_product()
+    l = _bind(lib)
+    assert packed.is_cuda and packed.is_contiguous()
+    offsets, sizes, count = _tables(offsets, sizes)
+    first_rows = np.ascontiguousarray(first_rows, dtype=np.uint32)
+    row_counts = np.ascontiguousarray(row_counts, dtype=np.uint32)
+    assert len(first_rows) == count and len(row_counts) == count and len(bands) == count
+    table, pitch, index_sizes = _pack_indexes(indexes, count)
+    dests = _frame_dests(bands, strides, capacities)
+    errcs = np.zeros(count, dtype=np.int32)
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    stream = torch.cuda.current_stream(packed.device).cuda_stream
+    rc = l.charls_amd_decode_rows_batch_device_ragged(count, packed.data_ptr(), offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p),
+                                                      table.ctypes.data, pitch, index_sizes.ctypes.data_as(u64p), first_rows.ctypes.data_as(u32p),
+                                                      row_counts.ctypes.data_as(u32p), dests, errcs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      C.c_void_p(stream))
+    if rc != 0:
+        raise capi.JpegLSError(rc, "charls_amd_decode_rows_batch_device_ragged")
+    return errcs
 
 
 def measure_counters(lib=None):

@@ -46,6 +46,7 @@ enum Knob : int
     kHostWindowFrames,      // CHARLS_AMD_HOST_WINDOW_FRAMES: most frames per window of the host-memory batch calls
     kHostStageBytes,        // CHARLS_AMD_HOST_STAGE_BYTES: pinned staging per lane for pageable caller memory
     kTranscodeWindowFrames, // CHARLS_AMD_TRANSCODE_WINDOW_FRAMES: frames per window of charls_amd_transcode_batch_device (its frame area)
+    kIndexWindowFrames,     // CHARLS_AMD_INDEX_WINDOW_FRAMES: frames per window of the index-only build's scratch frames (part 2l)
     kCount
 };
 
@@ -58,7 +59,7 @@ inline const char* name_of(int k)
                                               "TILE_SAMPLES", "PIXEL_MODE", "SPEC_CHUNK", "SPEC_WARM", "BATCH_ROUNDS", "COALESCE",
                                               "COALESCE_WAIT_US", "DECODE_WAVES_PER_CU", "DECODE_WORKGROUP_WAVES", "TRACE", "IDLE_RELEASE_MS", "NEAR_DECODE_PIXELS",
                                               "PACK_PASS_FRAMES", "HOST_LANES", "HOST_WINDOW_FRAMES", "HOST_STAGE_BYTES",
-                                              "TRANSCODE_WINDOW_FRAMES"};
+                                              "TRANSCODE_WINDOW_FRAMES", "INDEX_WINDOW_FRAMES"};
     return k >= 0 && k < kCount ? names[k] : nullptr;
 }
 

@@ -192,6 +192,9 @@ DeviceBuffer& pack_arena();
 // The calling thread's frames of charls_amd_transcode_batch_device (host/batch_transcode.cpp): a window of streams is decoded
 // into them and coded again from them (a work area: counted by work_area_bytes, freed by release_work_areas).
 DeviceBuffer& transcode_arena();
+// The calling thread's scratch frames of the index-only build (host/batch_index.cpp; charls_amd.h part 2l): the frames that get
+// no seek points are decoded into them, window by window, for their errc (a work area: counted and freed as the others).
+DeviceBuffer& index_scratch_arena();
 // The calling thread's buffers of the seek-point index's batch calls (host/batch_index.cpp): seek points, work items, descs,
 // results, hash jobs (work areas: counted by work_area_bytes, freed by release_work_areas).
 constexpr int kSeekArenas = 6;

@@ -375,6 +375,11 @@ DeviceBuffer& transcode_arena()
     return work_buffer(WorkBuffer::transcode);
 }
 
+DeviceBuffer& index_scratch_arena()
+{
+    return work_buffer(WorkBuffer::index_scratch);
+}
+
 DeviceBuffer& seek_arena(int which)
 {
     return areas().buffers[static_cast<int>(WorkBuffer::seek_first) + which];

@@ -165,7 +165,8 @@ __global__ void __launch_bounds__(64) decode_scans_wave_emit(const ScanDesc* __r
                 decode_line<S, 1>(t, m, br, line + j * ps, ps, d.width, corner + j, run_index[j], lane);
         if (br.err != kOk)
             break;
-        line_to_row<S>(d, line, ps, d.pixels + (size_t)y * d.pixel_stride, lane);
+        if (d.pixels != nullptr) // (wave-uniform; an index-only build has nowhere to put rows: a seek point is the LDS line)
+            line_to_row<S>(d, line, ps, d.pixels + (size_t)y * d.pixel_stride, lane);
         JLS_LOCKSTEP();
         if (--left_in_interval == 0 && y + 1 < d.height)
         {

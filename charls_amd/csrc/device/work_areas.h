@@ -19,6 +19,7 @@ enum class WorkBuffer : int
     plane,    // private stream buffers of the planar batch encoder
     pack,     // staging slots of the packed batch encoder
     transcode, // decoded frames of a window of charls_amd_transcode_batch_device
+    index_scratch, // scratch frames of the index-only build: the frames that get no seek points, a window at a time
     // restart-interval decode (launch_decode_intervals) and encode (launch_encode_intervals)
     marks,
     counts,

@@ -425,9 +425,11 @@ void probe_frames(StreamWindows& win, const BatchDests& to, charls_amd_codec_par
     t.count = 2;
 }
 
+} // namespace
+
 // A destination per frame of the caller's own: stride and capacity against the whole frame -- the rows of all planes of a
-// planar frame --, before any of its scans is decoded.
-void check_ragged_dests(StreamWindows& win, const BatchDests& to)
+// planar frame --, before any of its scans is decoded.  (stream_windows.h: the indexed calls of batch_index.cpp make the same check.)
+void jls::check_ragged_dests(StreamWindows& win, const BatchDests& to)
 {
     for (uint32_t i = 0; i < win.fr.size(); ++i)
     {
@@ -443,6 +445,8 @@ void check_ragged_dests(StreamWindows& win, const BatchDests& to)
         x.done = x.errc != CHARLS_JPEGLS_ERRC_SUCCESS;
     }
 }
+
+namespace {
 
 // A decode past the headers: the streams, the launches, where the frames go and what the caller learns of their parameters.
 struct BatchDecode

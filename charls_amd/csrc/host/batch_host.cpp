@@ -872,6 +872,54 @@ void transcode_host(uint32_t frame_count, const void* packed_in, const uint64_t*
     offsets_out[frame_count] = carry.at;
 }
 
+// charls_amd_index_batch_host (charls_amd.h part 2l): the index-only build on a host blob, the windows one after another on ONE
+// lane as those of transcode_host -- streams up into a 16-byte granular device window, the device call's body
+// (batch_index.cpp: index_packed_frames) on it.  Nothing comes down: indexes, sizes, parameters and errcs are host memory that
+// the body writes itself.
+void index_host(uint32_t frame_count, const void* packed, const uint64_t* offsets, const uint64_t* sizes, uint32_t lines, void* indexes,
+                size_t index_pitch_bytes, uint64_t* index_sizes, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs)
+{
+    const auto* in = static_cast<const uint8_t*>(packed);
+    std::vector<uint64_t> weights(frame_count);
+    for (uint32_t f = 0; f < frame_count; ++f)
+        weights[f] = align_up(static_cast<size_t>(sizes[f]), 16) + 16;
+    Shape shape;
+    shape.budget = dev::work_area_budget_beside(lanes_hold());
+    shape.lanes = 1;
+    shape.own = shape.budget / 2; // (the lane's blob; the areas of the device call's body get the other half)
+    shape.thread_limit = std::max<size_t>(shape.budget - shape.own, 1);
+    shape.stage_bytes = static_cast<size_t>(std::max<long long>(knobs::get_or(knobs::kHostStageBytes, kDefaultStageBytes), kMinStageBytes));
+    const long long forced_window = knobs::get_or(knobs::kHostWindowFrames, 0);
+    shape.window_end = hs::plan_windows(weights, forced_window >= 1 ? static_cast<uint32_t>(std::min<long long>(forced_window, UINT32_MAX)) : frame_count,
+                                        shape.own);
+
+    auto window = [&](Lane& lane, uint32_t w) {
+        const uint32_t first = w == 0 ? 0 : shape.window_end[w - 1], last = shape.window_end[w], n = last - first;
+        Copier copy{lane, shape.stage_bytes, nullptr};
+        // (+ 32: the decoders load whole aligned 16-byte groups; the margin behind the last stream is part of the allocation)
+        size_t in_bytes = 32;
+        for (uint32_t f = first; f < last; ++f)
+            in_bytes += align_up(static_cast<size_t>(sizes[f]), 16);
+        auto* d_in = static_cast<uint8_t*>(lane.blob.ensure(in_bytes));
+        lane.account();
+        std::vector<uint64_t> w_offsets(n);
+        size_t stream_at = 0;
+        for (uint32_t k = 0; k < n; ++k)
+        {
+            const uint32_t f = first + k;
+            copy.up(d_in + stream_at, in + offsets[f], static_cast<size_t>(sizes[f]), static_cast<size_t>(sizes[f]), 1);
+            w_offsets[k] = stream_at;
+            stream_at += align_up(static_cast<size_t>(sizes[f]), 16);
+        }
+        hip_check(hipStreamSynchronize(lane.stream));
+        index_packed_frames(n, d_in, w_offsets.data(), sizes + first, lines, static_cast<uint8_t*>(indexes) + static_cast<size_t>(first) * index_pitch_bytes,
+                            index_pitch_bytes, index_sizes + first, params_out != nullptr ? params_out + first : nullptr, errcs + first, lane.stream);
+    };
+    const charls_jpegls_errc rc = on_lanes(shape, window, [] {});
+    if (rc != CHARLS_JPEGLS_ERRC_SUCCESS)
+        raise(rc);
+}
+
 } // namespace
 
 // charls_amd_release_work_areas (misc_api.cpp): what the lanes hold, device and pinned.  The threads stay.
@@ -1195,6 +1243,36 @@ try
     transcode_host(frame_count, packed_in, offsets_in, sizes_in, specs, spec_count, budgets, near_candidates, candidate_count, packed_out,
                    packed_capacity_bytes, offset_alignment, offsets_out, sizes_out, near_out, params_out, errcs);
     transcode_near_of_uncoded(frame_count, errcs, near_out);
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}
+
+// ---- part 2l on a host blob: the index-only build
+extern "C" charls_jpegls_errc charls_amd_index_batch_host(uint32_t frame_count, const void* packed, const uint64_t* offsets, const uint64_t* sizes,
+                                                          uint32_t lines_per_seek_point, void* indexes, size_t index_pitch_bytes,
+                                                          uint64_t* index_sizes, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs)
+try
+{
+    check_pointer(offsets);
+    check_pointer(sizes);
+    check_pointer(index_sizes);
+    check_pointer(errcs);
+    check_argument(lines_per_seek_point > 0);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    check_pointer(packed);
+    check_pointer(indexes);
+    for (uint32_t f = 0; f < frame_count; ++f)
+    {
+        uint64_t end;
+        if (__builtin_add_overflow(offsets[f], sizes[f], &end))
+            raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+    }
+    dev::require_device();
+    index_host(frame_count, packed, offsets, sizes, lines_per_seek_point, indexes, index_pitch_bytes, index_sizes, params_out, errcs);
     return CHARLS_JPEGLS_ERRC_SUCCESS;
 }
 catch (...)

@@ -11,7 +11,12 @@
 //           one resume launch per group for all scans of all frames.
 //   bands:  as use, with the work items of decode_rows.
 // A frame whose index does not hold, or that gets no seek points, is decoded in the same call by the ordinary launches
-// (charls_amd_decode_batch_device on every run of such frames).
+// (decode_batch_streams on every run of such frames).
+//
+// The three bodies (build_indexes, decode_through_indexes, decode_bands) take the streams as StreamWindows -- an offset per
+// stream -- and a destination, capacity and stride per frame.  The slot calls of part 2c state i * pitch, the pitch and their
+// one stride; the calls of part 2l hand over the caller's tables, and the index-only build hands over no destinations at all
+// (index_packed_frames: pass A without pixels, pass B into scratch frames for the frames that get no seek points).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,8 +24,10 @@
 #include <functional>
 #include <vector>
 
+#include "../device/knobs.h"
 #include "../device/runtime.h"
 #include "../device/seek_decode.h"
+#include "batch_streams.h"
 #include "common.h"
 #include "preset.h"
 #include "seek_index.h"
@@ -56,19 +63,20 @@ void timings_end() noexcept
     t.count = 2;
 }
 
-// The scan whose header x's reader has read, decoding to `frames + i * frame_pitch` with the checks
-// charls_amd_decode_batch_device makes (stride, extent).  No line scratch.
-ScanDesc frame_scan_desc(const StreamWindows& s, uint32_t i, const BatchFrame& x, uint8_t* frames, size_t frame_pitch, uint32_t stride_arg)
+// The scan whose header x's reader has read, decoding to `dest` with the checks charls_amd_decode_batch_device makes
+// (stride, extent).  No line scratch.  dest == nullptr (the index-only build): rows of minimal stride that go nowhere --
+// decode_scans_wave_emit stores no row of a scan without pixels; no other kernel is handed such a scan.
+ScanDesc frame_scan_desc(const StreamWindows& s, uint32_t i, const BatchFrame& x, const charls_amd_frame_dest* dest)
 {
     const ScanSpec spec = scan_spec_of(x.reader);
-    const auto [row, stride] = row_and_stride(x.reader, stride_arg);
+    const auto [row, stride] = row_and_stride(x.reader, dest != nullptr ? dest->stride : 0);
     if (stride < row)
         raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_STRIDE);
     const size_t need = stride * spec.height - (stride - row); // (a scan of ILV_NONE is one component)
-    if (frame_pitch < x.plane_offset + need)
+    if (dest != nullptr && dest->capacity_bytes < x.plane_offset + need)
         raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
     ScanDesc d = desc_of(spec);
-    d.pixels = frames + i * frame_pitch + x.plane_offset;
+    d.pixels = dest != nullptr ? static_cast<uint8_t*>(dest->d_pixels) + x.plane_offset : nullptr;
     d.pixel_stride = stride;
     d.stream = s.stream_ptr(i, x.cursor);
     d.stream_capacity = s.sizes[i] - x.cursor;
@@ -272,11 +280,11 @@ std::vector<uint64_t> device_hashes(const StreamWindows& s, const std::vector<se
     return out;
 }
 
-// Every run of frames marked in `ordinary` through charls_amd_decode_batch_device; params_out as that call documents it
-// (params_from: the lowest frame whose parameters it holds so far).
-charls_jpegls_errc decode_ordinary(const StreamWindows& s, size_t stream_pitch, const std::vector<uint8_t>& ordinary, uint8_t* frames,
-                                   size_t frame_pitch, uint32_t stride, charls_amd_codec_params* params_out, uint32_t& params_from,
-                                   charls_jpegls_errc* errcs)
+// Every run of frames marked in `ordinary` through the batch decoder (batch_api.cpp: decode_batch_streams) with the streams'
+// offsets and the frames' destinations as they are here.  params_out as charls_amd_decode_batch_device documents it
+// (params_from: the lowest frame whose parameters it holds so far), or, `ragged`, as an array.
+void decode_ordinary(const StreamWindows& s, const std::vector<uint8_t>& ordinary, const charls_amd_frame_dest* dests, bool ragged,
+                     charls_amd_codec_params* params_out, uint32_t& params_from, charls_jpegls_errc* errcs)
 {
     const uint32_t n = static_cast<uint32_t>(ordinary.size());
     for (uint32_t i = 0; i < n;)
@@ -290,19 +298,49 @@ charls_jpegls_errc decode_ordinary(const StreamWindows& s, size_t stream_pitch, 
         while (last < n && ordinary[last])
             ++last;
         charls_amd_codec_params got{};
-        const charls_jpegls_errc rc =
-            charls_amd_decode_batch_device(last - i, s.slots + s.offset_of(i), stream_pitch, s.sizes + i, frames + i * frame_pitch, frame_pitch,
-                                           stride, &got, errcs + i, s.stream);
-        if (rc != CHARLS_JPEGLS_ERRC_SUCCESS)
-            return rc;
-        if (params_out && got.frame_info.width != 0 && i < params_from)
+        decode_batch_streams(last - i, s.slots, s.offsets() + i, s.sizes + i, BatchDests{dests + i, ragged, nullptr},
+                             ragged ? (params_out != nullptr ? params_out + i : nullptr) : &got, errcs + i, s.stream);
+        if (!ragged && params_out && got.frame_info.width != 0 && i < params_from)
         { // (the run's lowest frame that got as far as a scan is not known: no frame before the run's first can be it)
             *params_out = got;
             params_from = i;
         }
         i = last;
     }
-    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+
+// The frames of a slot call as a table of destinations: frame i at base + i * pitch, `pitch` bytes, one stride.
+std::vector<charls_amd_frame_dest> slot_dests(uint32_t count, void* base, size_t pitch, uint32_t stride)
+{
+    std::vector<charls_amd_frame_dest> dests(count);
+    for (uint32_t i = 0; i < count; ++i)
+        dests[i] = charls_amd_frame_dest{static_cast<uint8_t*>(base) + i * pitch, pitch, stride, 0};
+    return dests;
+}
+
+// The whole-call checks the calls of part 2l share: the tables, the destinations where there are any, the offsets.  Raises;
+// needs no device.  frame_count == 0 passes with any d_packed.
+void check_packed_index_call(uint32_t frame_count, const void* packed, const uint64_t* offsets, const uint64_t* sizes,
+                             const charls_amd_frame_dest* dests, const uint64_t* index_sizes, const charls_jpegls_errc* errcs)
+{
+    check_pointer(offsets);
+    check_pointer(sizes);
+    check_pointer(index_sizes);
+    check_pointer(errcs);
+    for (uint32_t f = 0; dests != nullptr && f < frame_count; ++f)
+    {
+        check_argument(dests[f].reserved == 0);
+        check_buffer(dests[f].d_pixels, dests[f].capacity_bytes);
+    }
+    if (frame_count == 0)
+        return;
+    check_pointer(packed);
+    for (uint32_t f = 0; f < frame_count; ++f)
+    {
+        uint64_t end;
+        if (__builtin_add_overflow(offsets[f], sizes[f], &end))
+            raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+    }
 }
 
 // set_index for every frame that has one: parsed[i] (empty scans: none), errors to the frame.
@@ -372,30 +410,28 @@ catch (...)
     return current_exception_to_errc();
 }
 
-extern "C" charls_jpegls_errc charls_amd_decode_batch_device_and_index(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
-                                                                       const uint64_t* sizes, void* d_frames, size_t frame_pitch_bytes,
-                                                                       uint32_t stride_arg, uint32_t lines, void* indexes,
-                                                                       size_t index_pitch_bytes, uint64_t* index_sizes,
-                                                                       charls_amd_codec_params* params_out, charls_jpegls_errc* errcs,
-                                                                       void* hip_stream)
-try
+namespace {
+
+// charls_amd_decode_batch_device_and_index behind its whole-call checks, on frames whose headers are read (s.read_headers).
+// Frame i of `s` goes to dests[i]; what the call reports of it -- index, index size, errc, and params_out where `ragged` makes
+// that an array -- goes to element slot_of[i] of the caller's arrays (slot_of == nullptr: element i).  `ragged`: the
+// destinations are a table of the caller's own, checked against the whole frame before anything of it is decoded.
+// dests == nullptr is the index-only build: every scan goes through the emit kernel without pixels.  A frame that gets no
+// seek points there -- by its header, or for a scan it meets later -- is marked in `set_aside` and left to the caller, who
+// gives it somewhere to decode to; what is reported of it here does not count.
+void build_indexes(StreamWindows& s, const charls_amd_frame_dest* dests, bool ragged, uint32_t lines, const uint32_t* slot_of, void* indexes,
+                   size_t index_pitch_bytes, uint64_t* index_sizes, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs,
+                   std::vector<uint8_t>* set_aside)
 {
-    check_pointer(sizes);
-    check_pointer(errcs);
-    check_pointer(index_sizes);
-    check_argument(lines > 0);
-    if (frame_count == 0)
-        return CHARLS_JPEGLS_ERRC_SUCCESS;
-    check_pointer(d_streams);
-    check_pointer(d_frames);
-    check_pointer(indexes);
-    dev::require_device();
-    auto stream = static_cast<hipStream_t>(hip_stream);
-    auto* frames = static_cast<uint8_t*>(d_frames);
-    const std::vector<uint64_t> stream_at = slot_offsets(frame_count, stream_pitch_bytes, sizes);
-    StreamWindows s(frame_count, d_streams, stream_at.data(), sizes, stream);
-    timings_begin();
-    s.read_headers(true);
+    const uint32_t frame_count = static_cast<uint32_t>(s.fr.size());
+    const hipStream_t stream = s.stream;
+    const auto out = [&](uint32_t i) { return slot_of != nullptr ? slot_of[i] : i; };
+    const auto aside = [&](uint32_t i) {
+        (*set_aside)[i] = 1;
+        s.fr[i].done = true;
+    };
+    if (dests != nullptr && ragged)
+        check_ragged_dests(s, BatchDests{dests, true, nullptr});
 
     struct Build
     {
@@ -407,7 +443,7 @@ try
     for (uint32_t i = 0; i < frame_count; ++i)
     {
         BatchFrame& x = s.fr[i];
-        index_sizes[i] = 0;
+        index_sizes[out(i)] = 0;
         if (x.done)
             continue;
         try
@@ -416,6 +452,8 @@ try
             builds[i].header = x.reader;
             builds[i].first = scan_spec_of(x.reader);
             builds[i].index.lines = lines;
+            if (dests == nullptr && (x.reader.height_from_dnl() || !seek_spec_eligible(builds[i].first)))
+                aside(i); // (by its header the frame gets no seek points: it needs somewhere to decode to)
         }
         catch (const error& e)
         {
@@ -428,6 +466,7 @@ try
     // not report; the launcher's clock is not reported, so it must not fail the call)
     DecodeLauncher plain(stream, true);
     uint32_t params_from = UINT32_MAX;
+    const auto stride_of = [&](uint32_t i) { return dests != nullptr ? dests[i].stride : 0u; };
     for (size_t scan_no = 0;; ++scan_no)
     {
         std::vector<uint32_t> emit_frames, plain_frames;
@@ -441,8 +480,10 @@ try
                 continue;
             try
             {
-                const ScanDesc d = frame_scan_desc(s, i, x, frames, frame_pitch_bytes, stride_arg);
-                if (params_out && i < params_from)
+                const ScanDesc d = frame_scan_desc(s, i, x, dests != nullptr ? dests + i : nullptr);
+                if (params_out && ragged)
+                    params_out[out(i)] = params_of(x.reader);
+                else if (params_out && i < params_from)
                 {
                     *params_out = params_of(x.reader);
                     params_from = i;
@@ -453,8 +494,13 @@ try
                 IndexScan& rec = b.index.scans[scan_no];
                 const bool eligible = !x.reader.height_from_dnl() && same_scan_parameters(spec, b.first) && seek_spec_eligible(spec) && rows_aligned(d);
                 rec.points = eligible ? seek::points_per_scan(spec.height, lines) : 0u;
+                if (dests == nullptr && !eligible)
+                { // (an ordinary scan after all: the ordinary launch needs rows to store to)
+                    aside(i);
+                    continue;
+                }
                 rec.data.assign(static_cast<size_t>(rec.points) * seek_point_bytes(spec), 0);
-                if (rec.points != 0)
+                if (rec.points != 0 || dests == nullptr) // (without pixels a scan too short for a point goes this way too)
                 {
                     emit_frames.push_back(i);
                     emit_descs.push_back(d);
@@ -492,7 +538,7 @@ try
                 x.done = true;
                 return;
             }
-            if (r.bytes > sizes[i] - x.cursor)
+            if (r.bytes > s.sizes[i] - x.cursor)
             { // (cannot happen: a scan is decoded from the bytes of its stream; the hash kernel must not be handed more)
                 x.errc = CHARLS_JPEGLS_ERRC_INVALID_DATA;
                 x.done = true;
@@ -504,7 +550,7 @@ try
             x.decoded_components += x.reader.scan_component_count();
             const bool end = x.decoded_components == x.reader.component_count();
             if (!end)
-                x.plane_offset += row_and_stride(x.reader, stride_arg).stride * x.reader.frame_info().height;
+                x.plane_offset += row_and_stride(x.reader, stride_of(i)).stride * x.reader.frame_info().height;
             which.push_back(i);
             bases.push_back(x.cursor);
             last.push_back(end ? 1 : 0);
@@ -525,8 +571,8 @@ try
             x.done = true; // the end of the image has been read: the index is the frame's
             try
             {
-                index_sizes[which[k]] = write_index(builds[which[k]].header, builds[which[k]].index,
-                                                    static_cast<uint8_t*>(indexes) + which[k] * index_pitch_bytes, index_pitch_bytes);
+                index_sizes[out(which[k])] = write_index(builds[which[k]].header, builds[which[k]].index,
+                                                         static_cast<uint8_t*>(indexes) + out(which[k]) * index_pitch_bytes, index_pitch_bytes);
             }
             catch (const error& e)
             {
@@ -535,7 +581,36 @@ try
         }
     }
     for (uint32_t i = 0; i < frame_count; ++i)
-        errcs[i] = s.fr[i].errc;
+        errcs[out(i)] = s.fr[i].errc;
+}
+
+} // namespace
+
+extern "C" charls_jpegls_errc charls_amd_decode_batch_device_and_index(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
+                                                                       const uint64_t* sizes, void* d_frames, size_t frame_pitch_bytes,
+                                                                       uint32_t stride_arg, uint32_t lines, void* indexes,
+                                                                       size_t index_pitch_bytes, uint64_t* index_sizes,
+                                                                       charls_amd_codec_params* params_out, charls_jpegls_errc* errcs,
+                                                                       void* hip_stream)
+try
+{
+    check_pointer(sizes);
+    check_pointer(errcs);
+    check_pointer(index_sizes);
+    check_argument(lines > 0);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    check_pointer(d_streams);
+    check_pointer(d_frames);
+    check_pointer(indexes);
+    dev::require_device();
+    auto stream = static_cast<hipStream_t>(hip_stream);
+    const std::vector<uint64_t> stream_at = slot_offsets(frame_count, stream_pitch_bytes, sizes);
+    const std::vector<charls_amd_frame_dest> dests = slot_dests(frame_count, d_frames, frame_pitch_bytes, stride_arg);
+    StreamWindows s(frame_count, d_streams, stream_at.data(), sizes, stream);
+    timings_begin();
+    s.read_headers(true);
+    build_indexes(s, dests.data(), false, lines, nullptr, indexes, index_pitch_bytes, index_sizes, params_out, errcs, nullptr);
     timings_end();
     return CHARLS_JPEGLS_ERRC_SUCCESS;
 }
@@ -612,28 +687,17 @@ void walk_indexed_frames(StreamWindows& s, const std::vector<SeekIndex>& parsed,
 
 } // namespace
 
-extern "C" charls_jpegls_errc charls_amd_decode_batch_device_indexed(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
-                                                                     const uint64_t* sizes, const void* indexes, size_t index_pitch_bytes,
-                                                                     const uint64_t* index_sizes, void* d_frames, size_t frame_pitch_bytes,
-                                                                     uint32_t stride_arg, charls_amd_codec_params* params_out,
-                                                                     charls_jpegls_errc* errcs, void* hip_stream)
-try
+namespace {
+
+// charls_amd_decode_batch_device_indexed behind its whole-call checks, on frames whose headers are read: frame i of `s`
+// through the index_sizes[i] bytes at indexes + i * index_pitch_bytes to dests[i].  `ragged`: the destinations are a table
+// of the caller's own, checked against the whole frame up front, and params_out is an array.
+void decode_through_indexes(StreamWindows& s, const void* indexes, size_t index_pitch_bytes, const uint64_t* index_sizes,
+                            const charls_amd_frame_dest* dests, bool ragged, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs)
 {
-    check_pointer(sizes);
-    check_pointer(errcs);
-    check_pointer(index_sizes);
-    if (frame_count == 0)
-        return CHARLS_JPEGLS_ERRC_SUCCESS;
-    check_pointer(d_streams);
-    check_pointer(d_frames);
-    check_pointer(indexes);
-    dev::require_device();
-    auto stream = static_cast<hipStream_t>(hip_stream);
-    auto* frames = static_cast<uint8_t*>(d_frames);
-    const std::vector<uint64_t> stream_at = slot_offsets(frame_count, stream_pitch_bytes, sizes);
-    StreamWindows s(frame_count, d_streams, stream_at.data(), sizes, stream);
-    timings_begin();
-    s.read_headers(true);
+    const uint32_t frame_count = static_cast<uint32_t>(s.fr.size());
+    if (ragged)
+        check_ragged_dests(s, BatchDests{dests, true, nullptr});
     std::vector<SeekIndex> parsed;
     parse_indexes(s, indexes, index_pitch_bytes, index_sizes, parsed);
 
@@ -641,7 +705,7 @@ try
     std::vector<BatchFrame> probe;
     std::vector<Walk> walks;
     walk_indexed_frames(s, parsed, probe, walks,
-                        [&](uint32_t i, const BatchFrame& y, size_t) { return frame_scan_desc(s, i, y, frames, frame_pitch_bytes, stride_arg); }, true);
+                        [&](uint32_t i, const BatchFrame& y, size_t) { return frame_scan_desc(s, i, y, dests + i); }, true);
     std::vector<uint8_t> ordinary(frame_count, 0);
     std::vector<uint8_t> with_points(frame_count, 0); // the frame's index has seek points: decoding it from the top is a fallback
     for (uint32_t i = 0; i < frame_count; ++i)
@@ -705,7 +769,7 @@ try
             scan_of.emplace_back(k, c);
         }
     }
-    run_resume(scans, stream);
+    run_resume(scans, s.stream);
     for (size_t k = 0; k < scans.size(); ++k)
     {
         Walk& w = walks[scan_of[k].first];
@@ -739,7 +803,9 @@ try
         s.fr[w.frame].done = true;
         ordinary[w.frame] = 0;
         from_points += w.descs.size();
-        if (params_out && w.frame < params_from)
+        if (params_out && ragged)
+            params_out[w.frame] = params_of(s.fr[w.frame].reader);
+        else if (params_out && w.frame < params_from)
         {
             *params_out = params_of(s.fr[w.frame].reader);
             params_from = w.frame;
@@ -750,42 +816,51 @@ try
     add_index_counters(from_points, 0, fallbacks, 0);
     for (uint32_t i = 0; i < frame_count; ++i)
         errcs[i] = s.fr[i].errc;
-    const charls_jpegls_errc rc = decode_ordinary(s, stream_pitch_bytes, ordinary, frames, frame_pitch_bytes, stride_arg, params_out, params_from, errcs);
+    decode_ordinary(s, ordinary, dests, ragged, params_out, params_from, errcs);
+}
+
+} // namespace
+
+extern "C" charls_jpegls_errc charls_amd_decode_batch_device_indexed(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
+                                                                     const uint64_t* sizes, const void* indexes, size_t index_pitch_bytes,
+                                                                     const uint64_t* index_sizes, void* d_frames, size_t frame_pitch_bytes,
+                                                                     uint32_t stride_arg, charls_amd_codec_params* params_out,
+                                                                     charls_jpegls_errc* errcs, void* hip_stream)
+try
+{
+    check_pointer(sizes);
+    check_pointer(errcs);
+    check_pointer(index_sizes);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    check_pointer(d_streams);
+    check_pointer(d_frames);
+    check_pointer(indexes);
+    dev::require_device();
+    auto stream = static_cast<hipStream_t>(hip_stream);
+    const std::vector<uint64_t> stream_at = slot_offsets(frame_count, stream_pitch_bytes, sizes);
+    const std::vector<charls_amd_frame_dest> dests = slot_dests(frame_count, d_frames, frame_pitch_bytes, stride_arg);
+    StreamWindows s(frame_count, d_streams, stream_at.data(), sizes, stream);
+    timings_begin();
+    s.read_headers(true);
+    decode_through_indexes(s, indexes, index_pitch_bytes, index_sizes, dests.data(), false, params_out, errcs);
     timings_end(); // (this call's seek and hash launches, not the ordinary launches of the frames that went that way)
-    return rc;
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
 }
 catch (...)
 {
     return current_exception_to_errc();
 }
 
-extern "C" charls_jpegls_errc charls_amd_decode_rows_batch_device(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
-                                                                  const uint64_t* sizes, const void* indexes, size_t index_pitch_bytes,
-                                                                  const uint64_t* index_sizes, const uint32_t* first_rows,
-                                                                  const uint32_t* row_counts, void* d_bands, size_t band_pitch_bytes,
-                                                                  uint32_t stride_arg, charls_jpegls_errc* errcs, void* hip_stream)
-try
+namespace {
+
+// charls_amd_decode_rows_batch_device behind its whole-call checks, on frames whose headers are read: rows [first_rows[i],
+// first_rows[i] + row_counts[i]) of frame i of `s` to bands[i], in decode_rows' layout at bands[i].stride.
+void decode_bands(StreamWindows& s, const void* indexes, size_t index_pitch_bytes, const uint64_t* index_sizes, const uint32_t* first_rows,
+                  const uint32_t* row_counts, const charls_amd_frame_dest* bands, charls_jpegls_errc* errcs)
 {
-    check_pointer(sizes);
-    check_pointer(errcs);
-    check_pointer(index_sizes);
-    check_pointer(first_rows);
-    check_pointer(row_counts);
-    if (frame_count == 0)
-        return CHARLS_JPEGLS_ERRC_SUCCESS;
-    check_pointer(d_streams);
-    check_pointer(d_bands);
-    dev::require_device();
-    auto stream = static_cast<hipStream_t>(hip_stream);
-    auto* bands = static_cast<uint8_t*>(d_bands);
-    const std::vector<uint64_t> stream_at = slot_offsets(frame_count, stream_pitch_bytes, sizes);
-    StreamWindows s(frame_count, d_streams, stream_at.data(), sizes, stream);
-    timings_begin();
-    s.read_headers(true);
+    const uint32_t frame_count = static_cast<uint32_t>(s.fr.size());
     std::vector<SeekIndex> parsed;
-    for (uint32_t i = 0; i < frame_count; ++i)
-        if (index_sizes[i] != 0)
-            check_pointer(indexes);
     parse_indexes(s, indexes, index_pitch_bytes, index_sizes, parsed);
 
     // decode_rows' argument checks; the stride of every frame
@@ -801,10 +876,10 @@ try
             check_argument(row_counts[i] > 0 && first_rows[i] < f.height && row_counts[i] <= f.height - first_rows[i]);
             const ScanSpec first = scan_spec_of(x.reader);
             const size_t row_bytes = row_bytes_of(first);
-            const size_t stride = stride_arg == 0 ? row_bytes : stride_arg;
+            const size_t stride = bands[i].stride == 0 ? row_bytes : bands[i].stride;
             check_argument(stride >= row_bytes, CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_STRIDE);
             const size_t needed = checked_mul(checked_mul(stride, row_counts[i]), scans_of_frame(x.reader)) - (stride - row_bytes);
-            check_argument(band_pitch_bytes >= needed, CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+            check_argument(bands[i].capacity_bytes >= needed, CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
             strides[i] = stride;
         }
         catch (const error& e)
@@ -815,7 +890,7 @@ try
     }
     auto band_desc = [&](uint32_t i, const BatchFrame& y, size_t c) {
         ScanDesc d = desc_of(scan_spec_of(y.reader));
-        d.pixels = bands + i * band_pitch_bytes + strides[i] * row_counts[i] * c;
+        d.pixels = static_cast<uint8_t*>(bands[i].d_pixels) + strides[i] * row_counts[i] * c;
         d.pixel_stride = strides[i];
         d.stream = s.stream_ptr(i, y.cursor);
         d.stream_capacity = s.sizes[i] - y.cursor;
@@ -939,7 +1014,7 @@ try
             walk_of.push_back(k);
         }
     }
-    run_resume(scans, stream);
+    run_resume(scans, s.stream);
     add_index_counters(from_points, 0, 0, 0);
     for (size_t k = 0; k < scans.size(); ++k)
     {
@@ -963,18 +1038,246 @@ try
         const size_t scans_n = scans_of_frame(x.reader);
         const size_t frame_bytes = checked_mul(checked_mul(row_bytes, f.height), scans_n);
         auto* area = static_cast<uint8_t*>(dev::seek_arena(kArenaFrame).ensure(frame_bytes));
-        const charls_jpegls_errc rc = charls_amd_decode_batch_device(1, s.slots + s.offset_of(i), stream_pitch_bytes, sizes + i, area,
-                                                                     frame_bytes, 0, nullptr, errcs + i, hip_stream);
-        if (rc != CHARLS_JPEGLS_ERRC_SUCCESS)
-            return rc;
+        const charls_amd_frame_dest whole_frame{area, frame_bytes, 0, 0};
+        decode_batch_streams(1, s.slots, s.offsets() + i, s.sizes + i, BatchDests{&whole_frame, false, nullptr}, nullptr, errcs + i, s.stream);
         if (errcs[i] != CHARLS_JPEGLS_ERRC_SUCCESS)
             continue;
         for (size_t c = 0; c < scans_n; ++c)
-            hip_check(hipMemcpy2DAsync(bands + i * band_pitch_bytes + strides[i] * row_counts[i] * c, strides[i],
+            hip_check(hipMemcpy2DAsync(static_cast<uint8_t*>(bands[i].d_pixels) + strides[i] * row_counts[i] * c, strides[i],
                                        area + row_bytes * f.height * c + row_bytes * first_rows[i], row_bytes, row_bytes, row_counts[i],
-                                       hipMemcpyDeviceToDevice, stream));
-        hip_check(hipStreamSynchronize(stream));
+                                       hipMemcpyDeviceToDevice, s.stream));
+        hip_check(hipStreamSynchronize(s.stream));
     }
+}
+
+} // namespace
+
+extern "C" charls_jpegls_errc charls_amd_decode_rows_batch_device(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
+                                                                  const uint64_t* sizes, const void* indexes, size_t index_pitch_bytes,
+                                                                  const uint64_t* index_sizes, const uint32_t* first_rows,
+                                                                  const uint32_t* row_counts, void* d_bands, size_t band_pitch_bytes,
+                                                                  uint32_t stride_arg, charls_jpegls_errc* errcs, void* hip_stream)
+try
+{
+    check_pointer(sizes);
+    check_pointer(errcs);
+    check_pointer(index_sizes);
+    check_pointer(first_rows);
+    check_pointer(row_counts);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    check_pointer(d_streams);
+    check_pointer(d_bands);
+    dev::require_device();
+    auto stream = static_cast<hipStream_t>(hip_stream);
+    const std::vector<uint64_t> stream_at = slot_offsets(frame_count, stream_pitch_bytes, sizes);
+    for (uint32_t i = 0; i < frame_count; ++i)
+        if (index_sizes[i] != 0)
+            check_pointer(indexes);
+    const std::vector<charls_amd_frame_dest> bands = slot_dests(frame_count, d_bands, band_pitch_bytes, stride_arg);
+    StreamWindows s(frame_count, d_streams, stream_at.data(), sizes, stream);
+    timings_begin();
+    s.read_headers(true);
+    decode_bands(s, indexes, index_pitch_bytes, index_sizes, first_rows, row_counts, bands.data(), errcs);
+    timings_end();
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}
+
+// ---- part 2l: the same three bodies on a packed blob, with the caller's table of destinations or with none ------------------
+
+// The index-only build behind its whole-call checks (frame_count >= 1, a device is there; timings are the caller's).
+//   Pass A: every frame that by its header is all seek points, through the emit kernel without pixels.
+//   Pass B: the frames pass A set aside -- no seek points by their header, or an ordinary scan met later --, through the same
+//           body into scratch frames, window by window: dev::index_scratch_arena, a quarter of what the thread's work areas may
+//           grow to (as the frame area of part 2j), or INDEX_WINDOW_FRAMES frames.  A frame that cannot be given a scratch
+//           frame gets not_enough_memory.
+void jls::index_packed_frames(uint32_t frame_count, const void* d_packed, const uint64_t* offsets, const uint64_t* sizes, uint32_t lines,
+                              void* indexes, size_t index_pitch_bytes, uint64_t* index_sizes, charls_amd_codec_params* params_out,
+                              charls_jpegls_errc* errcs, void* hip_stream)
+{
+    constexpr size_t kFrameAlignment = 256; // (a scratch frame starts on one: 16-bit rows are never at an odd address)
+    auto stream = static_cast<hipStream_t>(hip_stream);
+    if (params_out != nullptr)
+        std::fill(params_out, params_out + frame_count, charls_amd_codec_params{});
+    std::vector<uint8_t> aside(frame_count, 0);
+    std::vector<uint32_t> later;  // the frames of pass B, in the caller's order
+    std::vector<size_t> want;     // what each takes in the area
+    std::vector<uint64_t> bytes;  // its frame, packed
+    {
+        StreamWindows s(frame_count, d_packed, offsets, sizes, stream);
+        s.read_headers(true);
+        build_indexes(s, nullptr, true, lines, nullptr, indexes, index_pitch_bytes, index_sizes, params_out, errcs, &aside);
+        for (uint32_t f = 0; f < frame_count; ++f)
+        {
+            if (!aside[f])
+                continue;
+            index_sizes[f] = 0;
+            try
+            {
+                const charls_frame_info& fi = s.fr[f].reader.frame_info();
+                const size_t frame = checked_mul(checked_mul(checked_mul(static_cast<size_t>(fi.component_count), fi.height), fi.width),
+                                                 bytes_per_sample(fi.bits_per_sample));
+                later.push_back(f);
+                bytes.push_back(frame);
+                want.push_back(checked_mul(frame / kFrameAlignment + 1, kFrameAlignment));
+            }
+            catch (const error& e)
+            {
+                errcs[f] = e.code;
+            }
+        }
+    }
+    if (later.empty())
+        return;
+
+    // ---- the windows of pass B, planned as those of transcode_frames are
+    const uint32_t n_later = static_cast<uint32_t>(later.size());
+    const size_t budget = dev::work_area_budget();
+    const long long forced = knobs::get_or(knobs::kIndexWindowFrames, 0);
+    size_t room = forced >= 1 ? SIZE_MAX : std::max<size_t>(budget / 4, 1);
+    uint32_t most = forced >= 1 ? static_cast<uint32_t>(std::min<long long>(forced, n_later)) : n_later;
+    std::vector<uint32_t> window_end; // one past the last frame of every window (positions in `later`)
+    uint8_t* area = nullptr;
+    const bool limited = dev::workspace_limit() != 0 && budget < *std::max_element(want.begin(), want.end());
+    while (!limited)
+    {
+        window_end.clear();
+        size_t filled = 0, most_filled = 0;
+        uint32_t held = 0;
+        for (uint32_t k = 0; k < n_later; ++k)
+        {
+            if (held != 0 && (held == most || want[k] > room - std::min(filled, room)))
+            {
+                window_end.push_back(k);
+                most_filled = std::max(most_filled, filled);
+                filled = 0;
+                held = 0;
+            }
+            filled += want[k];
+            ++held;
+        }
+        window_end.push_back(n_later);
+        most_filled = std::max(most_filled, filled);
+        area = static_cast<uint8_t*>(dev::try_ensure(dev::index_scratch_arena(), most_filled + kFrameAlignment));
+        if (area != nullptr || window_end.size() == n_later) // (windows of one frame each: nothing smaller to ask for)
+            break;
+        room = std::max<size_t>(room / 2, 1);
+        most = (most + 1) / 2;
+    }
+    if (area == nullptr)
+    {
+        for (const uint32_t f : later)
+            errcs[f] = CHARLS_JPEGLS_ERRC_NOT_ENOUGH_MEMORY;
+        return;
+    }
+    std::vector<uint64_t> w_offsets, w_sizes;
+    std::vector<charls_amd_frame_dest> w_dests;
+    for (uint32_t w = 0, first = 0; w < window_end.size(); first = window_end[w++])
+    {
+        const uint32_t n = window_end[w] - first;
+        w_offsets.resize(n);
+        w_sizes.resize(n);
+        w_dests.resize(n);
+        size_t at = 0;
+        for (uint32_t k = 0; k < n; ++k)
+        {
+            const uint32_t f = later[first + k];
+            w_offsets[k] = offsets[f];
+            w_sizes[k] = sizes[f];
+            w_dests[k] = charls_amd_frame_dest{area + at, bytes[first + k], 0, 0};
+            at += want[first + k];
+        }
+        StreamWindows s(n, d_packed, w_offsets.data(), w_sizes.data(), stream);
+        s.read_headers(true);
+        build_indexes(s, w_dests.data(), true, lines, later.data() + first, indexes, index_pitch_bytes, index_sizes, params_out, errcs, nullptr);
+    }
+}
+
+extern "C" charls_jpegls_errc charls_amd_index_batch_device_packed(uint32_t frame_count, const void* d_packed, const uint64_t* offsets,
+                                                                   const uint64_t* sizes, const charls_amd_frame_dest* dests, uint32_t lines,
+                                                                   void* indexes, size_t index_pitch_bytes, uint64_t* index_sizes,
+                                                                   charls_amd_codec_params* params_out, charls_jpegls_errc* errcs,
+                                                                   void* hip_stream)
+try
+{
+    check_packed_index_call(frame_count, d_packed, offsets, sizes, dests, index_sizes, errcs);
+    check_argument(lines > 0);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    check_pointer(indexes);
+    dev::require_device();
+    timings_begin();
+    if (dests == nullptr)
+        index_packed_frames(frame_count, d_packed, offsets, sizes, lines, indexes, index_pitch_bytes, index_sizes, params_out, errcs, hip_stream);
+    else
+    {
+        if (params_out != nullptr)
+            std::fill(params_out, params_out + frame_count, charls_amd_codec_params{});
+        StreamWindows s(frame_count, d_packed, offsets, sizes, static_cast<hipStream_t>(hip_stream));
+        s.read_headers(true);
+        build_indexes(s, dests, true, lines, nullptr, indexes, index_pitch_bytes, index_sizes, params_out, errcs, nullptr);
+    }
+    timings_end();
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}
+
+extern "C" charls_jpegls_errc charls_amd_decode_batch_device_ragged_indexed(uint32_t frame_count, const void* d_packed, const uint64_t* offsets,
+                                                                            const uint64_t* sizes, const void* indexes,
+                                                                            size_t index_pitch_bytes, const uint64_t* index_sizes,
+                                                                            const charls_amd_frame_dest* dests,
+                                                                            charls_amd_codec_params* params_out, charls_jpegls_errc* errcs,
+                                                                            void* hip_stream)
+try
+{
+    check_pointer(dests);
+    check_packed_index_call(frame_count, d_packed, offsets, sizes, dests, index_sizes, errcs);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    check_pointer(indexes);
+    dev::require_device();
+    if (params_out != nullptr)
+        std::fill(params_out, params_out + frame_count, charls_amd_codec_params{});
+    StreamWindows s(frame_count, d_packed, offsets, sizes, static_cast<hipStream_t>(hip_stream));
+    timings_begin();
+    s.read_headers(true);
+    decode_through_indexes(s, indexes, index_pitch_bytes, index_sizes, dests, true, params_out, errcs);
+    timings_end(); // (this call's seek and hash launches, not the ordinary launches of the frames that went that way)
+    return CHARLS_JPEGLS_ERRC_SUCCESS;
+}
+catch (...)
+{
+    return current_exception_to_errc();
+}
+
+extern "C" charls_jpegls_errc charls_amd_decode_rows_batch_device_ragged(uint32_t frame_count, const void* d_packed, const uint64_t* offsets,
+                                                                         const uint64_t* sizes, const void* indexes, size_t index_pitch_bytes,
+                                                                         const uint64_t* index_sizes, const uint32_t* first_rows,
+                                                                         const uint32_t* row_counts, const charls_amd_frame_dest* bands,
+                                                                         charls_jpegls_errc* errcs, void* hip_stream)
+try
+{
+    check_pointer(bands);
+    check_pointer(first_rows);
+    check_pointer(row_counts);
+    check_packed_index_call(frame_count, d_packed, offsets, sizes, bands, index_sizes, errcs);
+    if (frame_count == 0)
+        return CHARLS_JPEGLS_ERRC_SUCCESS;
+    for (uint32_t f = 0; f < frame_count; ++f)
+        if (index_sizes[f] != 0)
+            check_pointer(indexes);
+    dev::require_device();
+    StreamWindows s(frame_count, d_packed, offsets, sizes, static_cast<hipStream_t>(hip_stream));
+    timings_begin();
+    s.read_headers(true);
+    decode_bands(s, indexes, index_pitch_bytes, index_sizes, first_rows, row_counts, bands, errcs);
     timings_end();
     return CHARLS_JPEGLS_ERRC_SUCCESS;
 }

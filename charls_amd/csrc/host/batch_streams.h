@@ -57,6 +57,14 @@ void decode_batch_salvage_indexed(uint32_t frame_count, const void* d_packed, co
                                   charls_amd_codec_params* params_out, charls_amd_salvage_report* reports, uint8_t* interval_status,
                                   size_t status_pitch_bytes, charls_jpegls_errc* errcs, void* hip_stream);
 
+// The index-only build of charls_amd_index_batch_device_packed (batch_index.cpp; charls_amd.h part 2l) behind its whole-call
+// checks, which the host form (batch_host.cpp) runs on every device window: frame f's index to indexes + f * index_pitch_bytes
+// (HOST), its size to index_sizes[f], no pixels anywhere but in a work area of the calling thread.  params_out (an array) may
+// be nullptr.  frame_count >= 1, a device is there.  Raises.
+void index_packed_frames(uint32_t frame_count, const void* d_packed, const uint64_t* offsets, const uint64_t* sizes,
+                         uint32_t lines_per_seek_point, void* indexes, size_t index_pitch_bytes, uint64_t* index_sizes,
+                         charls_amd_codec_params* params_out, charls_jpegls_errc* errcs, void* hip_stream);
+
 // The batch encoder behind charls_amd_encode_batch_device with every frame's pixels named by a pointer of its own
 // (d_pixels: HOST array of frame_count DEVICE pointers; the slot call passes d_frames + i * frame_pitch_bytes): frame i's
 // .jls goes to d_streams + i * stream_pitch_bytes.  `frame_bytes` is what every frame offers from its pointer on (the slot

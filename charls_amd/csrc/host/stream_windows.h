@@ -185,6 +185,8 @@ public:
         }
     }
 
+    const uint64_t* offsets() const noexcept { return stream_at_; } // the table the object was made with
+
     const uint8_t* slots;
     const uint64_t* sizes;
     hipStream_t stream;
@@ -195,6 +197,12 @@ private:
     dev::DeviceBuffer d_specs_, d_windows_;
     dev::PinnedBuffer h_specs_, h_windows_;
 };
+
+// The whole-frame checks of a destination table of the caller's own (batch_streams.h: BatchDests with `ragged`), on frames
+// whose headers are read: a stride below the frame's row is invalid_argument_stride, a capacity below the rows of all its
+// planes invalid_argument_size, and the frame is done.  Defined in batch_api.cpp.
+struct BatchDests;
+void check_ragged_dests(StreamWindows& win, const BatchDests& to);
 
 // The ordinary decoder launches for a set of scans of any geometry.  The device copies of the descriptors and results and
 // the line scratch live as long as the object: a caller that decodes in rounds reuses them.

@@ -497,7 +497,9 @@ CHARLS_AMD_API int32_t charls_amd_index_counters(uint64_t* out, int32_t capacity
  * decode_rows_batch_device: rows [first_rows[f], first_rows[f] + row_counts[f]) of frame f in decode_rows' layout at
  *   d_bands + f * band_pitch_bytes (a band_pitch_bytes below what the band needs: invalid_argument_size for that frame).
  *   index_sizes[f] == 0: from the top.  Frames without seek points, and planar frames without an index, are decoded whole
- *   into a work area on the ordinary path and the band is copied out (damage below the band is then reported too). */
+ *   into a work area on the ordinary path and the band is copied out (damage below the band is then reported too).
+ * These three take fixed-pitch slots and one frame pitch; part 2l has them on a packed blob with a destination per frame, and
+ * an index-only build that needs no frames at all. */
 CHARLS_AMD_API charls_jpegls_errc charls_amd_index_size_bound(const charls_amd_codec_params* params,
                                                               uint32_t lines_per_seek_point, size_t* bytes);
 CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_device_and_index(
@@ -518,7 +520,8 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_rows_batch_device(
  * of offsets -- the form files, archives, DICOM multi-frame pixel data and charls_amd_gather hold them in -- instead of
  * fixed-pitch slots.  Frame f's .jls is the sizes[f] bytes at d_packed + offsets[f].  `offsets`, `sizes` and `errcs` are HOST
  * arrays; the return value, hip_stream, stride and params_out are those of part 2.  New entry points beside the slot
- * calls: those, the indexed calls of part 2c and the multi-device calls of part 2b stay on slots.
+ * calls: those and the multi-device calls of part 2b stay on slots; the indexed calls of part 2c take packed streams in
+ * part 2l.
  *
  * The offset rule (pack_streams, encode_batch_device_packed): offsets[0] = 0 and offsets[f + 1] = offsets[f] + sizes[f]
  * rounded up to `offset_alignment`, a power of two in [1, 4096] (anything else: invalid_argument for the whole call, before
@@ -601,8 +604,8 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_device_packed(uint32_t
  *   staging slots of its own, and the whole window is packed by ONE launch of the copy kernel, the running offset carrying
  *   from window to window.  The staging is the work area of charls_amd_encode_batch_device_packed under its rule (a quarter
  *   of what the thread's work areas may hold; not_enough_memory when a configured workspace limit does not cover the
- *   largest frame's slot).  Not done: the groups of a window run one after another, not on side streams; the indexed calls
- *   of part 2c and the multi-device calls of part 2b stay as they are; the tile pipeline has no mixed-geometry launch (a
+ *   largest frame's slot).  Not done: the groups of a window run one after another, not on side streams; the
+ *   multi-device calls of part 2b stay as they are (the indexed calls of part 2c take ragged frames in part 2l); the tile pipeline has no mixed-geometry launch (a
  *   batch of many geometries with few frames each pays one set of launches per geometry and window).
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct charls_amd_frame_source /* encode: one frame of a ragged batch */
@@ -1058,6 +1061,78 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_transcode_batch_host_budget(
     const charls_amd_transcode_spec* specs, uint32_t spec_count, const uint64_t* budgets, const int32_t* near_candidates,
     uint32_t candidate_count, void* packed_out, size_t packed_capacity_bytes, uint32_t offset_alignment, uint64_t* offsets_out,
     uint64_t* sizes_out, int32_t* near_out, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Part 2l -- the SEEK-POINT INDEX on PACKED streams: part 2c joined with parts 2d, 2e and 2i.  The calls of part 2c take
+ * fixed-pitch slots and a frame per stream; an ingest job that wants the sidecars of a blob had to copy every stream into a
+ * slot, allocate a full frame per stream and throw the pixels away.  Here the streams are a packed blob with an offset
+ * table (part 2d: frame f's .jls is the sizes[f] bytes at d_packed + offsets[f]; the readability rule of part 2d applies),
+ * the destinations are the table of part 2e -- or there are none --, and the indexes are HOST memory at
+ * indexes + f * index_pitch_bytes as in parts 2c and 2h.  `offsets`, `sizes`, `errcs`, `index_sizes`, `first_rows`,
+ * `row_counts` and `params_out` are HOST arrays of frame_count elements; params_out is an ARRAY as in part 2e, may be NULL, and
+ * is zeroed for a frame that did not get as far as its first scan.  New entry points beside the existing ones, none of which
+ * changes.
+ *
+ * The contract per frame is part 2c's, which is part 1's.  The index bytes are byte for byte what
+ * charls_amd_decode_batch_device_and_index and charls_amd_jpegls_decoder_decode_to_buffer_and_index write for the same stream
+ * and K: an index built here is accepted by parts 1, 2c and 2h, and the reverse.  Pixels, bands and errcs are those of the
+ * slot calls on the same bytes, and the checks of a destination are those of charls_amd_decode_batch_device_ragged: a
+ * stride below the frame's row is invalid_argument_stride for that frame, a capacity_bytes below the frame (the band) is
+ * invalid_argument_size for that frame, both are checked against the whole frame once its header is read, and nothing of a
+ * frame that fails them is written.  An index_pitch_bytes below the frame's get_index_size is invalid_argument_size for that
+ * frame: nothing of it is decoded and index_sizes[f] is 0.  One frame's failure never changes another frame's result, and
+ * nothing is written outside a frame's own extent of its destination or index slot.
+ *
+ * Whole-call errors, all checked before a device is asked for and before anything is written: NULL tables,
+ * lines_per_seek_point == 0, a `reserved` that is not 0, a d_pixels of NULL with a capacity_bytes that is not 0
+ * (invalid_argument); offsets[f] + sizes[f] that overflows (invalid_argument_size).  frame_count == 0 returns success.
+ *
+ * index_batch_device_packed: builds every frame's index, K = lines_per_seek_point.  With `dests` it is
+ *   charls_amd_decode_batch_device_and_index on the blob and the caller's destinations (a 16-bit frame at an odd address or
+ *   stride gets its pixels and an index without seek points, as there).  With dests == NULL it is the INDEX-ONLY build:
+ *   errcs[f] is the code the frame would get with a destination of minimal stride -- the stream is decoded in full, only the
+ *   pixels have nowhere to go -- and no caller memory but indexes, index_sizes, params_out and errcs is written.  The frames
+ *   that are all seek points go through the kernel that writes them without a pixel pointer: no frame is allocated for
+ *   them (a 16-bit frame is never at an odd address here, so it gets its seek points).  The frames that get no seek points
+ *   in part 2c (restart intervals, a height from DNL, a scan the exact decoder does not take, a later scan whose parameters
+ *   differ from the first scan's) get the index without seek points that part 2c writes, and are decoded for their errc
+ *   into scratch frames: one more work area of the calling thread, filled in windows within a quarter of what its work areas
+ *   may hold (knob INDEX_WINDOW_FRAMES), counted by charls_amd_work_area_bytes and freed by charls_amd_release_work_areas; when
+ *   not one such frame fits, those frames get not_enough_memory.
+ * decode_batch_device_ragged_indexed: charls_amd_decode_batch_device_indexed on the blob, frame f going to dests[f]
+ *   (index_sizes[f] == 0: frame f has no index and decodes the ordinary way, as does a frame whose index does not hold).
+ * decode_rows_batch_device_ragged: charls_amd_decode_rows_batch_device on the blob: rows [first_rows[f], first_rows[f] +
+ *   row_counts[f]) of frame f in decode_rows' layout at bands[f].d_pixels with bands[f].stride; a capacity_bytes below what the
+ *   band needs is invalid_argument_size for that frame.  `indexes` may be NULL when every index_sizes[f] is 0.
+ * index_batch_host: the index-only build with the blob in HOST memory of any kind (part 2i: pinned memory is copied from
+ *   directly, pageable memory through the lane's staging); there is no hip_stream argument and the call returns when the
+ *   results are there.  Results are those of the device call on a device copy of the same bytes.  Windows run one after
+ *   another on ONE lane of part 2i, as those of charls_amd_transcode_batch_host do -- the streams go up into a 16-byte
+ *   granular device window, the body of the device call runs on it, and nothing comes down but what that body returns to the
+ *   host anyway (HOST_WINDOW_FRAMES forces the window length).
+ *
+ * charls_amd_index_counters and charls_amd_last_timings are those of part 2c: the launches of the seek kernels are one per
+ * group of scans and scan ordinal (pass), whatever form the streams come in.
+ * Not done: the multi-device calls of part 2b; a host form of the indexed decode and of the bands; seek points from the
+ *   group decoder (the index-only build runs the exact decoder, one wavefront per scan).
+ * ---------------------------------------------------------------------------------------------------------------- */
+CHARLS_AMD_API charls_jpegls_errc charls_amd_index_batch_device_packed(
+    uint32_t frame_count, const void* d_packed, const uint64_t* offsets, const uint64_t* sizes,
+    const charls_amd_frame_dest* dests /* NULL: index only */, uint32_t lines_per_seek_point, void* indexes,
+    size_t index_pitch_bytes, uint64_t* index_sizes, charls_amd_codec_params* params_out, charls_jpegls_errc* errcs,
+    void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_batch_device_ragged_indexed(
+    uint32_t frame_count, const void* d_packed, const uint64_t* offsets, const uint64_t* sizes, const void* indexes,
+    size_t index_pitch_bytes, const uint64_t* index_sizes, const charls_amd_frame_dest* dests,
+    charls_amd_codec_params* params_out, charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_rows_batch_device_ragged(
+    uint32_t frame_count, const void* d_packed, const uint64_t* offsets, const uint64_t* sizes, const void* indexes,
+    size_t index_pitch_bytes, const uint64_t* index_sizes, const uint32_t* first_rows, const uint32_t* row_counts,
+    const charls_amd_frame_dest* bands, charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API charls_jpegls_errc charls_amd_index_batch_host(
+    uint32_t frame_count, const void* packed, const uint64_t* offsets, const uint64_t* sizes, uint32_t lines_per_seek_point,
+    void* indexes, size_t index_pitch_bytes, uint64_t* index_sizes, charls_amd_codec_params* params_out,
+    charls_jpegls_errc* errcs);
 
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */

@@ -7,7 +7,13 @@ synthetic frame of tools/one_frame_latency.py.  Run on the GPU box: python tools
 plain-batch figure of the same run: building N indexes in one call against N x one part-1 build, decoding N frames through
 K = 64 indexes against charls_amd_decode_batch_device, 64-row bands at K = 16 from N frames, and the GPU time of the
 segment-hash launches (charls_amd_last_timings [1]).  The N slots hold N copies of one stream: frames are independent, so
-the times are those of N different streams of that size.  --frames / --build-frames choose the N."""
+the times are those of N different streams of that size.  --frames / --build-frames choose the N.
+
+--batch --packed: the calls of part 2l on a packed blob (N copies of one stream back to back, alignment 1) beside the slot
+calls of part 2c on the same streams, the two sides alternating, --calls repeats after one warm-up each: (a) the index-only
+build against charls_amd_decode_batch_device_and_index -- of the library at --parent-lib where one is given (a build of the
+commit before part 2l), else of this build --, with the frame memory the index-only build does not allocate; (b) the ragged
+indexed decode and the ragged bands against their slot calls.  --packed-frames is the N (256), K = 64 (bands: K = 16)."""
 import argparse
 import os
 import statistics
@@ -28,6 +34,9 @@ ap.add_argument("--frames", type=int, nargs="*", default=[1, 4, 16, 64, 256, 102
 ap.add_argument("--build-frames", type=int, nargs="*", default=[1, 16, 256, 1024])
 ap.add_argument("--band-frames", type=int, nargs="*", default=[1, 64, 1024])
 ap.add_argument("--images", nargs="*", default=["tulips_tiled", "synthetic"])
+ap.add_argument("--packed", action="store_true")
+ap.add_argument("--packed-frames", type=int, default=256)
+ap.add_argument("--parent-lib", default=None)
 args = ap.parse_args()
 lib = capi.load_product()
 
@@ -119,6 +128,108 @@ def batch_mode():
                   f" = {100 * hash_ms / (best * 1e3):.0f}%   N x part 1 = {N * b1:9.1f} ms", flush=True)
 
 
+def packed_mode():
+    import numpy as np
+    import torch
+    from charls_amd import batch
+
+    N, K, repeats = args.packed_frames, 64, args.calls
+    parent = capi.CharLSLibrary(args.parent_lib) if args.parent_lib else lib
+    mpix = N * n * n / 1e6
+
+    def alternate(sides):
+        """[(name, fn)] -> {name: [seconds per repeat]}: one warm-up each, then the sides in turn, repeat by repeat."""
+        for _, fn in sides:
+            fn()
+        times = {name: [] for name, _ in sides}
+        for _ in range(repeats):
+            for name, fn in sides:
+                torch.cuda.synchronize()
+                a = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times[name].append(time.perf_counter() - a)
+        return times
+
+    def report(what, times):
+        for name, ts in times.items():
+            print(f"  {what:<16} {name:<34} " + " ".join(f"{t * 1e3:9.1f}" for t in ts) +
+                  f" ms   median {statistics.median(ts) * 1e3:9.1f} ms = {mpix / statistics.median(ts):8.1f} MPix/s"
+                  f"   spread {(max(ts) - min(ts)) / statistics.median(ts) * 100:4.1f}%", flush=True)
+
+    for name, img in frames.items():
+        jls = lib.encode(img, width=n, height=n, bits_per_sample=8)
+        pitch = (len(jls) + 255) & ~255
+        print(f"{name} {n} x {n} 8-bit, N = {N}, K = {K}: {len(jls)} B per stream; slots of {pitch} B, blob of {N * len(jls)} B", flush=True)
+        one = torch.zeros(pitch, dtype=torch.uint8)
+        one[:len(jls)] = torch.frombuffer(bytearray(jls), dtype=torch.uint8)
+        d_streams = one.cuda().repeat(N, 1).contiguous()
+        blob = torch.cat([one[:len(jls)].repeat(N), torch.zeros(16, dtype=torch.uint8)]).cuda()
+        sizes = np.full(N, len(jls), dtype=np.uint64)
+        offsets = np.arange(N, dtype=np.uint64) * len(jls)
+        want = torch.from_numpy(img.reshape(-1)).cuda()
+        part1 = lib.decode_with_index(jls, K)[2]
+        bound = batch.index_size_bound(n, n, lines_per_seek_point=K, lib=lib)
+        # ---- (a) the index-only build against the slot build with frames
+        torch.cuda.synchronize()
+        free_before = torch.cuda.mem_get_info()[0]
+        out = torch.empty((N, n * n), dtype=torch.uint8, device="cuda")
+        got = {}
+
+        def slot_build():
+            got["slot"] = batch.decode_batch_and_index(d_streams, sizes, out, K, index_pitch=bound, lib=parent)
+
+        def index_only():
+            got["only"] = batch.index_batch_packed(blob, offsets, sizes, K, index_pitch=bound, lib=lib)
+
+        slot_name = "slot build + frames" + (" (parent)" if args.parent_lib else " (this build)")
+        times = alternate([(slot_name, slot_build), ("index-only, packed", index_only)])
+        report("(a) build", times)
+        for key in ("slot", "only"):
+            _, errcs, built = got[key]
+            assert (errcs == 0).all() and built[0] == part1 and built[-1] == part1, key
+        assert torch.equal(out[N - 1], want)
+        print(f"  (a) frame memory the index-only build does not take: {N * n * n / 2**20:.0f} MiB "
+              f"(free device memory fell by {(free_before - torch.cuda.mem_get_info()[0]) / 2**20:.0f} MiB when the slot side's frames were allocated); "
+              f"work areas held now: {batch.work_area_bytes(lib) / 2**20:.0f} MiB", flush=True)
+        # ---- (b) the ragged indexed decode and the ragged bands against their slot calls
+        outs = [out[f] for f in range(N)]
+        indexes = [part1] * N
+
+        def slot_indexed():
+            got["e"] = batch.decode_batch_indexed(d_streams, sizes, indexes, out, lib=lib)[1]
+
+        def ragged_indexed():
+            got["e"] = batch.decode_batch_ragged_indexed(blob, offsets, sizes, indexes, outs, lib=lib)[1]
+
+        for side in (slot_indexed, ragged_indexed):
+            out.zero_()
+            side()
+            assert (got["e"] == 0).all() and torch.equal(out[N - 1], want) and torch.equal(out[0], want)
+        report("(b) decode", alternate([("indexed, slots", slot_indexed), ("indexed, packed + ragged", ragged_indexed)]))
+        index16 = [lib.decode_with_index(jls, 16)[2]] * N
+        first = n // 2 - 32
+        band_want = want[first * n:(first + 64) * n]
+        bands = torch.empty((N, 64 * n), dtype=torch.uint8, device="cuda")
+        band_list = [bands[f] for f in range(N)]
+
+        def slot_bands():
+            got["e"] = batch.decode_rows_batch(d_streams, sizes, index16, [first] * N, [64] * N, bands, lib=lib)
+
+        def ragged_bands():
+            got["e"] = batch.decode_rows_batch_ragged(blob, offsets, sizes, index16, [first] * N, [64] * N, band_list, lib=lib)
+
+        for side in (slot_bands, ragged_bands):
+            bands.zero_()
+            side()
+            assert (got["e"] == 0).all() and torch.equal(bands[N - 1], band_want) and torch.equal(bands[0], band_want)
+        report("(b) 64-row bands", alternate([("bands K=16, slots", slot_bands), ("bands K=16, packed + ragged", ragged_bands)]))
+        del out, bands
+
+
+if args.batch and args.packed:
+    packed_mode()
+    sys.exit(0)
 if args.batch:
     batch_mode()
     sys.exit(0)
