@@ -579,6 +579,8 @@ int group_encode_lanes(const ScanDesc& d, uint32_t count)
     const bool shape = (d.interleave_mode != 0 && d.components >= 2 && d.components <= 4) || (d.interleave_mode == 0 && d.components == 1);
     if (!shape || encode_engine() == EncodeEngine::serial)
         return 0;
+    if (d.reset == 0)
+        return 0; // RESET = 256*m is stored as 0 by the reference: N is never halved and outgrows the 8 bits of the packed context
     int best = 0;
     for (int lanes = 64; lanes >= 8; lanes /= 2)
     {

@@ -195,8 +195,9 @@ JLS_DEV void put_bits(uint32_t* ring, uint32_t p, uint32_t v, int n)
 //
 // Two renderings.  Inside a scan -- every wanted lane's 16 bytes and the byte behind them are coded bytes that have a
 // predecessor, and no 0xFF is followed by a byte >= 0x80 -- a lane's bytes are ONE 128-bit number in the ring's bit order
-// from which the stuffed bits are deleted (one byte in 256 is followed by one; the wavefront loops as often as its busiest
-// lane has them, once or twice) and which then goes to the ring as five words.  The first bytes of a misaligned stream,
+// from which the stuffed bits are deleted (the wavefront loops as often as its busiest lane has them: once or twice on
+// ordinary streams, where one byte in 256 is followed by one, 8 times on a lane of FF 7F FF 7F ..., the worst case, which
+// tests/test_emu_stuffing.py counts) and which then goes to the ring as five words.  The first bytes of a misaligned stream,
 // the bytes around its end and anything that looks like a marker take the byte-by-byte rendering (refill_bytewise).
 template <int G>
 JLS_DEV void refill_bytewise(Producer& s, uint32_t* ring, bool want, int lane, int sub, uint64_t u0, const uint4& raw,

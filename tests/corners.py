@@ -286,7 +286,7 @@ ROUTES = {
     "seek_decode": _wave,
     # encoders
     "tile_encode": lambda c: c.near == 0,
-    "group_encode": lambda c: c.near != 0,
+    "group_encode": lambda c: c.near != 0 and _reset_byte(c) != 0,   # (its contexts keep N in 8 bits: RESET = 256 is the serial encoder's)
     "serial_encode": lambda c: True,
 }
 
@@ -302,18 +302,19 @@ EMU_ROUTES = {
     "pixel_decode": lambda c: ROUTES["pixel_decode"](c) and not c.long,
     "seek_decode": lambda c: _wave(c) and not c.long,
     "tile_encode": lambda c: c.near == 0 and not c.long,
-    "group_encode": lambda c: c.near != 0 and not c.long,
+    "group_encode": lambda c: ROUTES["group_encode"](c) and not c.long,
     "serial_encode": lambda c: True,
 }
 
 
-def route_frames(route, where="gpu"):
-    """The frames of a route on the MI355X ("gpu"), in the emulator ("emu") or in either ("any")."""
+def route_frames(route, where="gpu", corpus=None):
+    """The frames of a route on the MI355X ("gpu"), in the emulator ("emu") or in either ("any"); of `corpus` (another
+    {name: Corner}, tests/stuffing.py) where one is given."""
     tables = {"gpu": (ROUTES,), "emu": (EMU_ROUTES,), "any": (ROUTES, EMU_ROUTES)}[where]
-    return [n for n, c in CORPUS.items() if any(t[route](c) for t in tables)]
+    return [n for n, c in (CORPUS if corpus is None else corpus).items() if any(t[route](c) for t in tables)]
 
 
-def batches(names, by="geometry"):
+def batches(names, by="geometry", corpus=None):
     """Frames that can share a launch, {key: [names]} in the corpus' order, which puts different recipes side by side:
     "geometry"   one geometry and sample width: a decode batch of the API;
     "thresholds" and NEAR, T1..T3 as well: the scans of a wavefront of the group kernels share the gradient table, a scan with
@@ -321,7 +322,7 @@ def batches(names, by="geometry"):
     "parameters" and every coding parameter: an encode batch of the API."""
     out = {}
     for n in names:
-        c = CORPUS[n]
+        c = (CORPUS if corpus is None else corpus)[n]
         key = (c.width, c.height, c.bits, c.comps, c.ilv)
         if by == "thresholds":
             key += (c.near,) + tuple(coding_parameters(c)[1:4])

@@ -25,7 +25,7 @@ class Scan:
     """One scan of a corner frame: its pixels in the user's layout, the oracle's entropy-coded segment and what the oracle
     decodes from it."""
 
-    def __init__(self, c, index, start, end, jls, pixels):
+    def __init__(self, c, index, start, end, jls, pixels, misalignment=None):
         self.c, self.index = c, index
         self.nc = 1 if c.ilv == 0 else c.comps
         bps = 1 if c.bits <= 8 else 2
@@ -34,7 +34,7 @@ class Scan:
         self.source = np.frombuffer(c.img.tobytes(), dtype=np.uint8)[index * size:(index + 1) * size].copy()
         self.want = pixels[index * size:(index + 1) * size]
         self.segment = jls[start:end]
-        self.stream = _stream_copy(jls, start)
+        self.stream = _stream_copy(jls, start, misalignment)
         self.pc = corners.coding_parameters(c)
 
     def decode_desc(self, keep):

@@ -62,10 +62,12 @@ def test_emulated_encode_kernel_matches_reference_scan_bytes(c):
 DECODERS = ["emu_decode_scans_serial", "emu_decode_scans_wave"]
 
 
-def _stream_copy(jls, start):
-    """Source bytes of a scan placed at a deliberately odd offset of a padded buffer (the ring refill aligns down)."""
+def _stream_copy(jls, start, misalignment=None):
+    """Source bytes of a scan placed at a deliberately odd offset of a padded buffer (the ring refill aligns down): offset 19 of
+    the buffer, or, where `misalignment` is given, at an address that is `misalignment` mod 16."""
     raw = np.zeros(len(jls) - start + 64 + 32, dtype=np.uint8)
-    view = raw[19:19 + len(jls) - start]
+    at = 19 if misalignment is None else 16 + (misalignment - raw.ctypes.data) % 16
+    view = raw[at:at + len(jls) - start]
     view[:] = np.frombuffer(jls[start:], dtype=np.uint8)
     return view
 
