@@ -66,6 +66,21 @@ JLS_DEV uint32_t from_lane(uint32_t v, int l)
     return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
 }
 
+// Value of the lane below (lane - 1) in one DPP wave shift, no trip through LDS.  Lane 0 gets its own value back: the
+// caller replaces it.  All 64 lanes must be active -- a source lane that is switched off delivers nothing -- so the call
+// may not stand under a per-lane condition.  (The lane above is wave_shl:1, 0x130; nothing uses it yet.)
+#ifndef JLS_EMULATED
+JLS_DEV int lane_below(int v)
+{
+    return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xF, 0xF, false); // wave_shr:1
+}
+#else
+JLS_DEV int lane_below(int v)
+{
+    return __shfl_up(v, 1);
+}
+#endif
+
 // Median of three signed integers in one vector instruction (the compiler only forms v_med3_i32 for constant bounds).
 // med3s takes its last operand from a scalar register.
 #ifndef JLS_EMULATED

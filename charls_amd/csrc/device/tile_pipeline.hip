@@ -145,6 +145,16 @@ enum Counter : uint32_t
     } while (0)
 #endif
 
+// Parts of analyze_tiles / sort_tiles that can be switched off one by one for an A/B (CHARLS_AMD_CXXFLAGS=-DJLS_TILE_LANES=0
+// ...): in P2 of sort_tiles the neighbours of a sample from the lane next to it instead of LDS, in pass 2 of analyze_tiles
+// the carry into a piece by look-ahead.  The streams do not depend on them.
+#ifndef JLS_TILE_LANES
+#define JLS_TILE_LANES 1
+#endif
+#ifndef JLS_TILE_LOOKAHEAD
+#define JLS_TILE_LOOKAHEAD 1
+#endif
+
 // State of a job at its first event (after the warm-up) and behind its last one (N is a function of the event index);
 // bad: an event of the job would make the reference raise invalid_data.
 struct JobState
@@ -640,8 +650,13 @@ __global__ void __launch_bounds__(kThreads) analyze_tiles(const ScanDesc* __rest
     __syncthreads();
     JLS_PHASE(25);
     // ---- pass 2: run-mode state before every sample.  s' = eq & (s | q0) is a carry chain: generate = eq & q0,
-    // propagate = eq, so one 64-bit addition per chunk resolves 64 samples (src/scan_encoder_impl.hpp:249-275).  A piece
-    // that does not start its line first runs the (scalar) chain over the chunks before it.
+    // propagate = eq, so one 64-bit addition per chunk resolves 64 samples (src/scan_encoder_impl.hpp:249-275).
+    //
+    // The state a piece starts in (JLS_TILE_LOOKAHEAD).  The chain over the chunks in front of a piece is the same chain
+    // again: a chunk generates a carry where its own addition overflows and propagates one where its sum is all ones, so a
+    // lane per chunk, two ballots and one more 64-bit addition give the carry into the piece -- one trip for up to 64
+    // chunks (a line has at most 128) where the wavefront of a line's last piece walked all chunks in front of it one
+    // after the other while the others waited at the barrier.
     for (uint32_t sgm = wave; sgm < g.segments; sgm += kWaves)
     {
         const uint32_t r = sgm / g.pieces, piece = sgm % g.pieces;
@@ -650,18 +665,43 @@ __global__ void __launch_bounds__(kThreads) analyze_tiles(const ScanDesc* __rest
         const uint32_t k1 = k0 + g.chunks_per_piece < chunks ? k0 + g.chunks_per_piece : chunks;
         const auto key_row = global_ptr(w.keyinv) + (size_t)y * width;
         unsigned long long carry = 0;
-        for (uint32_t k = 0; k < k1; ++k)
+        if (JLS_TILE_LOOKAHEAD)
+        {
+            if (k0 < k1)
+                for (uint32_t kb = 0; kb < k0; kb += 64)
+                {
+                    const uint32_t k = kb + (uint32_t)lane, kc = k < k0 ? k : k0 - 1;
+                    const unsigned long long a = s_eq[r * chunks + kc];
+                    const unsigned long long b = a & s_q0[r * chunks + kc];
+                    const unsigned long long sum = a + b;
+                    // (a lane behind the piece's start passes the carry on to bit 63)
+                    const unsigned long long gen = __ballot(k < k0 && sum < a);
+                    const unsigned long long any = gen | __ballot(k >= k0 || sum == ~0ull);
+                    const unsigned long long in = (any + gen + carry) ^ any ^ gen; // bit i: carry into chunk kb + i
+                    carry = (((any & gen) | ((any | gen) & in)) >> 63) & 1ull;
+                }
+        }
+        else
+            for (uint32_t k = 0; k < k0 && k0 < k1; ++k)
+            {
+                const unsigned long long a = s_eq[r * chunks + k];
+                const unsigned long long b = a & s_q0[r * chunks + k];
+                const unsigned long long st = (a + b + carry) ^ a ^ b;
+                carry = (((a & b) | ((a | b) & st)) >> 63) & 1ull;
+            }
+        for (uint32_t k = k0; k < k1; ++k)
         {
             const unsigned long long a = s_eq[r * chunks + k];
-            const unsigned long long b = a & s_q0[r * chunks + k];
+            const unsigned long long q = s_q0[r * chunks + k];
+            const unsigned long long b = a & q;
             const unsigned long long sum = a + b + carry;
             const unsigned long long st = sum ^ a ^ b; // bit i: in-run state before sample i
             carry = (((a & b) | ((a | b) & st)) >> 63) & 1ull;
             const uint32_t x = k * 64 + lane;
-            if (k >= k0 && x < width)
+            if (x < width)
             {
                 const bool s = (st >> lane) & 1ull;
-                const bool q0 = (s_q0[r * chunks + k] >> lane) & 1ull;
+                const bool q0 = (q >> lane) & 1ull;
                 const bool eq = (a >> lane) & 1ull;
                 uint16_t key = s_key[r * width + x];
                 if (!(s || q0))
@@ -1038,6 +1078,26 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
         const uint32_t lane_bit = 1u << (lane & 31), below = lane_bit - 1u;
         const bool upper = lane >= 32;
         const uint32_t run_first = segoff[0];
+        // Neighbours from lanes (JLS_TILE_LANES): a lane reads x and Rb of its own column; Ra and Rc are the lane below's x
+        // and Rb, one wave shift each instead of a read of LDS.  Every lane loads and shifts in every chunk (a lane behind
+        // the line's end takes the line's last column and has no event).  Lane 0 takes what lane 63 of the chunk before
+        // held -- scalars carried across the trip; the edge samples in front of a line's first chunk, a read of LDS in front
+        // of a piece that starts inside the line.  The pair of the chunk behind is requested before this one is worked on.
+        int next_v = 0, next_rb = 0, last_v = edge_a, last_rb = edge_c;
+        auto pair_of = [&](uint32_t k, int& own, int& above) __attribute__((always_inline)) {
+            const uint32_t x = k * 64 + lane, xc = x < width ? x : width - 1;
+            own = (int)cur[xc] & mask;
+            above = (int)(cur - width)[xc] & mask;
+        };
+        if (JLS_TILE_LANES && k0 < k1)
+        {
+            pair_of(k0, next_v, next_rb);
+            if (k0 > 0)
+            {
+                last_v = (int)cur[k0 * 64 - 1] & mask;
+                last_rb = (int)(cur - width)[k0 * 64 - 1] & mask;
+            }
+        }
         for (uint32_t kb = k0; kb < k1; kb += 16)
         {
             if (!keys_kept)
@@ -1078,7 +1138,18 @@ __global__ void __launch_bounds__(kThreads) sort_tiles(const ScanDesc* __restric
                     // the record of a regular sample, worked out for every lane (no divergence; lanes without an event discard
                     // it); a run start leaves its column (the second of its two 2-byte slots is written with the record)
                     uint32_t record = 0;
-                    if (inside)
+                    if (JLS_TILE_LANES)
+                    {
+                        const int v = next_v, rb = next_rb;
+                        pair_of(kb + j + 1, next_v, next_rb);
+                        int ra = lane_below(v), rc = lane_below(rb);
+                        ra = lane == 0 ? last_v : ra;
+                        rc = lane == 0 ? last_rb : rc;
+                        last_v = (int)from_lane((uint32_t)v, 63);
+                        last_rb = (int)from_lane((uint32_t)rb, 63);
+                        record = make_record<S>(v, med3(ra + rb - rc, ra, rb), (key >> 9) & 1, t.maxval);
+                    }
+                    else if (inside)
                     {
                         const int v = (int)cur[x] & mask;
                         const int ra = x > 0 ? (int)cur[x - 1] & mask : edge_a;

@@ -6,7 +6,7 @@ tile_pipeline.hip count only when the library is built with CHARLS_AMD_CXXFLAGS=
     gpurun -- python tools/phase_clocks.py                                          (on the GPU box)
 
 Runs one encode step of bench.py's workload with 512 frames, sums the `phase_clocks` lines the library prints per call
-and prints each phase's share of its kernel's wavefront clocks (of a sample: every 64th workgroup counts -- with all of
+and prints each phase's share of its kernel's wavefront clocks and the clocks themselves (of a sample: every 64th workgroup counts -- with all of
 them counting, 75 M atomics on 22 addresses queue up in front of the kernels' own memory traffic and the shares
 measure the atomics).
 """
@@ -44,9 +44,9 @@ def main() -> None:
     print(f"{calls} calls of the tile pipeline")
     for kernel, names in NAMES.items():
         whole = sum(total[i] for i in names) or 1
-        print(f"{kernel}: {whole / 1e9:.1f} G clocks of wavefront time")
+        print(f"{kernel}: {whole / 1e9:.3f} G clocks of wavefront time")
         for i, name in names.items():
-            print(f"  {100.0 * total[i] / whole:5.1f} %  {name}")
+            print(f"  {100.0 * total[i] / whole:5.1f} %  {total[i] / 1e9:6.3f} G  {name}")
 
 
 if __name__ == "__main__":
