@@ -48,6 +48,18 @@ constexpr uint32_t kPrepRing = 128;
 constexpr uint32_t kPrepSlots = kPrepRing + 64;
 constexpr uint32_t kPrepChunk = 64;                // samples prepared per call
 constexpr int kStepsPerLoop = 63;                  // the step loop never consumes the last prepared sample (see prepare_line)
+// MED relative to Ra (8-bit containers; scan_group_step.inc has the same switch): the prepared entry is
+// {Rc | Rb << 8 | T << 16, Rb - Rc} and the predictor Ra + median(0, Rb - Ra, Rb - Rc), which reads Ra by its low byte only --
+// the lossless step of a MAXVAL = 255 scan then leaves its sample unmasked.  -DJLS_STEP_MED_FROM_RA=0: the entry {Rc | T << 16, Rb}
+// and median(Ra, Rb, Ra + Rb - Rc) for every sample width, as for wider samples.
+#ifndef JLS_STEP_MED_FROM_RA
+#define JLS_STEP_MED_FROM_RA 1
+#endif
+// The assembly's count of a call is a count of trips of two steps (scan_group_step.inc has the same switch, and
+// JLS_STEP_TRIP_POINTERS, which changes no value here): what the run service leaves of the count is whole trips.
+#ifndef JLS_STEP_TRIP_COUNT
+#define JLS_STEP_TRIP_COUNT 1
+#endif
 
 // LDS of a workgroup (one wavefront): the gradient table shared by its scans, then one region per scan.  A scan's line
 // starts one sample before a 16-byte boundary so that sample 1 (the first of the row) is aligned for the 16-byte row stores.
@@ -465,6 +477,7 @@ __global__ void __launch_bounds__(64 * W) decode_scans_group(const ScanDesc* __r
     constexpr int kScansPerWave = 64 / G;
     constexpr bool kWide = sizeof(S) > 1;
     constexpr bool kChecked = kWide || kNear; // codes may exceed the 32-bit window, |Errval| 65535, A 2^24: looked at
+    constexpr bool kRelative = JLS_STEP_MED_FROM_RA != 0 && !kWide; // prepared entries {Rc | Rb << 8 | T << 16, Rb - Rc}: MED relative to Ra
     JLS_DYNAMIC_LDS(smem);
     const int lane = W == 1 ? (int)threadIdx.x : (int)(threadIdx.x & 63u);
     const int wave = W == 1 ? 0 : (int)(threadIdx.x >> 6);
@@ -579,7 +592,8 @@ __global__ void __launch_bounds__(64 * W) decode_scans_group(const ScanDesc* __r
         return (int)lds_load<unsigned char>((uint32_t)(diff + cap)); // the table is at LDS address 0
     };
     // Entries of samples from .. from + kPrepChunk - 1 (those of the line): {Rc | T << 16, Rb} with T = 9 (9 q1 + q2), q1 of
-    // Rd - Rb, q2 of Rb - Rc.  Every lane of the group takes kPrepChunk / G consecutive samples: their kPer + 2 samples of the
+    // Rd - Rb, q2 of Rb - Rc; 8-bit containers (kRelative): {Rc | Rb << 8 | T << 16, Rb - Rc} -- T <= 5760 keeps to the upper
+    // half, the second word is a signed dword.  Every lane of the group takes kPrepChunk / G consecutive samples: their kPer + 2 samples of the
     // previous line, kPer + 1 gradients (q2 of a sample is q1 of its left neighbour).
     auto prepare = [&](bool want, uint32_t from, bool first_is_over) {
         constexpr uint32_t kPer = kPrepChunk / G;
@@ -605,7 +619,8 @@ __global__ void __launch_bounds__(64 * W) decode_scans_group(const ScanDesc* __r
             const uint32_t j = j0 + c;
             const uint32_t tt = (uint32_t)mad24(g[c + 1], 81, 9 * g[c]);
             const uint32_t slot = j & (kPrepRing - 1);
-            const PrepEntry entry{(uint32_t)v[c] | (tt << 16), (uint32_t)v[c + 1]};
+            const PrepEntry entry = kRelative ? PrepEntry{(uint32_t)v[c] | ((uint32_t)v[c + 1] << 8) | (tt << 16), (uint32_t)(v[c + 1] - v[c])}
+                                              : PrepEntry{(uint32_t)v[c] | (tt << 16), (uint32_t)v[c + 1]};
             if (want && j <= width)
             {
                 store_pair(prep_address + slot * 8u, entry);
@@ -743,12 +758,14 @@ __global__ void __launch_bounds__(64 * W) decode_scans_group(const ScanDesc* __r
                     mm_seen |= t_mm;
                 lm += lm_step; // now the slot of the previous step's sample; the slots behind it still hold the previous line
                 pp += pp_step;
-                // -- this step's LDS reads: the prepared entry {Rc | T << 16, Rb}, the bit window, Q3
+                // -- this step's LDS reads: the prepared entry {Rc | T << 16, Rb} (kRelative: {Rc | Rb << 8 | T << 16, Rb - Rc}), the
+                // bit window, Q3
                 const PrepEntry entry = load_pair(pp);
                 const uint64_t ring_words = ring_words_at(ring_address, p);
                 const int rc = kWide ? (int)(entry.x & 0xFFFFu) : (int)(entry.x & 0xFFu);
-                const int rb = (int)entry.y;
-                const int q3 = quantised(rc - a);
+                const int rb = kRelative ? (int)((entry.x >> 8) & 0xFFu) : (int)entry.y;
+                const int ra = kRelative ? (a & 0xFF) : a; // (kRelative: every reader of Ra takes its low byte -- `a` may be unmasked)
+                const int q3 = quantised(rc - ra);
                 // -- bookkeeping, part 2: A.12 / A.13, src/regular_mode_context.hpp:45-93 (|B| cannot overflow in lossless
                 // mode).  With N' the new N and tb = B + Errval (halved at a reset): delta = (tb > 0) - (tb + N' <= 0),
                 // B' = median(tb - delta * N', 1 - N', 0), C' = median(C + delta, -128, 127).
@@ -775,7 +792,9 @@ __global__ void __launch_bounds__(64 * W) decode_scans_group(const ScanDesc* __r
                 const uint32_t u = lowest_one(win); // length of the unary prefix; 0xFFFFFFFF for an all-zero window
                 u1 = u + 1u; // the window beyond the prefix: u1 = 32 only with k = 0, where no field is read
                 const uint32_t beyond = bit_reverse(win >> (u1 & 31u));
-                const int px0 = med3(a + (rb - rc), a, rb); // MED predictor = median(Ra, Rb, Ra + Rb - Rc), src/jpegls_algorithm.hpp:143-161
+                // MED predictor = median(Ra, Rb, Ra + Rb - Rc), src/jpegls_algorithm.hpp:143-161; kRelative: the same number as
+                // Ra + median(0, Rb - Ra, Rb - Rc), with Rb - Rc from the entry
+                const int px0 = kRelative ? ra + med3((int)entry.y, 0, rb - ra) : med3(a + (rb - rc), a, rb);
                 // A regular-mode sample whose code lies inside the 32-bit window.  8-bit samples: valid streams keep
                 // A / N < 2^9, so k <= 9, and u < LIMIT - qbpp - 1 <= 23 then bounds the code by 32 bits and |Errval| by
                 // 5888; k (and, for wider samples, the mapped error) are only accumulated here and examined after the
@@ -810,6 +829,8 @@ __global__ void __launch_bounds__(64 * W) decode_scans_group(const ScanDesc* __r
                     v += v < -near ? range_step : (v > maxval + near ? -range_step : 0);
                     a = med3(v, 0, maxval);
                 }
+                else if (kRelative && maxval == 255)
+                    a = mad24(e, sgn, px); // not reduced: its low byte is the sample (the store, Q3 and the predictor take that), masked behind the loop
                 else
                     a = mad24(e, sgn, px) & maxval; // every lane: a lane that could not decode reloads its Ra after the loop
                 k_last = (uint32_t)k;
@@ -895,13 +916,23 @@ __global__ void __launch_bounds__(64 * W) decode_scans_group(const ScanDesc* __r
                             }
                             JLS_LOCKSTEP();
                             ok_m |= served_m;
-                            // the count of steps left: no more than any served scan may still take
+                            // the count of steps left: no more than any served scan may still take.  The assembly counts TRIPS of two
+                            // steps (JLS_STEP_TRIP_COUNT; a call of an odd number of steps starts with the second half of one): `left`
+                            // is odd in the first step of a trip and even in its second, and what a served scan may still take is
+                            // rounded down to whole trips from there -- in a trip's first step: its second step and (v - 1) / 2 trips,
+                            // and when a scan may not even take that step, the loop ends here, as one that ended by count.  (lm and pp
+                            // are true pointers here; the assembly advances them once per trip, JLS_STEP_TRIP_POINTERS, and its copies
+                            // address by offsets.)
                             const uint32_t may_take = fits ? budget - taken : ~0u;
                             uint32_t left = 63u - (uint32_t)__builtin_clzll(ticker);
+                            const bool first_of_trip = JLS_STEP_TRIP_COUNT != 0 && (left & 1u) != 0;
                             for (LaneMask m = served_m; m != 0;)
                             {
                                 const uint32_t v = value_of_lowest_lane(m, may_take);
-                                left = v < left ? v : left;
+                                uint32_t whole = v;
+                                if (JLS_STEP_TRIP_COUNT != 0)
+                                    whole = first_of_trip ? (v == 0 ? 0u : 1u + ((v - 1u) & ~1u)) : (v & ~1u);
+                                left = whole < left ? whole : left;
                                 m &= ~lanes_where(may_take == v);
                             }
                             ticker = 1ull << left;
@@ -912,8 +943,9 @@ __global__ void __launch_bounds__(64 * W) decode_scans_group(const ScanDesc* __r
                 ticker = tick(ticker, in_line_m, ok_m);
             } while (ticker != 0);
 #else
-            // The same loop, written out for gfx950: 72 instructions per step for 8-bit samples (the compiler's rendering of the
-            // C++ above: 88), scheduled by hand so that the three LDS round trips of the chain (Q3 <- the gradient table,
+            // The same loop, written out for gfx950: 67.5 instructions per step for 8-bit samples (the compiler's rendering of the
+            // C++ above: 88), two steps per trip with ONE count test and ONE pointer advance per trip, scheduled by hand so
+            // that the three LDS round trips of the chain (Q3 <- the gradient table,
             // the context record, and before them the prepared entry, which is requested one step ahead) are covered by the
             // previous step's context update, the bit window and the predictor.  Lanes outside their line are switched off
             // (EXEC) for the whole loop.  Hazards kept by hand: two instructions between a v_cmp and the VALU that reads its mask.
@@ -941,6 +973,8 @@ __global__ void __launch_bounds__(64 * W) decode_scans_group(const ScanDesc* __r
                 ok_m = in_line_m & ~fail_m;
             }
 #endif
+            if (kRelative && !kNear)
+                a &= maxval; // (the MAXVAL = 255 step leaves its sample unmasked; the assembly's epilogue has masked it already)
             win_stopped = win_now;
             // the bookkeeping owed to the lanes whose last step decoded a sample
             bool owed_last;
@@ -1231,7 +1265,8 @@ __global__ void __launch_bounds__(64 * W) decode_scans_group(const ScanDesc* __r
         if (__any(slow))
         {
             JLS_PATH(9); // unusual codes
-            const int rc = kWide ? (int)(entry_stopped.x & 0xFFFFu) : (int)(entry_stopped.x & 0xFFu), rb = (int)entry_stopped.y;
+            const int rc = kWide ? (int)(entry_stopped.x & 0xFFFFu) : (int)(entry_stopped.x & 0xFFu);
+            const int rb = kRelative ? (int)((entry_stopped.x >> 8) & 0xFFu) : (int)entry_stopped.y;
             const int s = qs8 >> 31;
             const int idx = ((qs8 ^ s) - s) >> 3;
             const Record rec = records[idx];

@@ -19,12 +19,13 @@
 //     of the previous step, the request of the bit window, the predictor and A.13 of the previous step; the context record
 //     under bit window, unary prefix, sign and the prefix test; the prepared entry of the NEXT sample is requested in the
 //     middle of a step, behind the last use of this step's.
-//   * two steps per trip of the loop (a taken branch costs more than a not-taken one).
+//   * two steps per trip of the loop (a taken branch costs more than a not-taken one), and the trip is the unit of the count and
+//     of the pointer advances (JLS_STEP_TRIP_COUNT, JLS_STEP_TRIP_POINTERS below).
 // Lanes outside their line are switched off (EXEC) for the whole loop.
 //
 // Fixed registers (v80 - v127, s80 - s99 are clobbered; v80 - v92: the rare path; v93 = RESET; v94 - v99: near-lossless constants):
 // v100 = 2912 (8 * 364), v101 = byte selector of v_perm, v102 = -cap
-// (wide), v103 = 127, v104 = -128, v105 = 1; temporaries v108 - v117; pairs: E = v[118:119] / v[106:107] entry {Rc | T << 16, Rb} of the
+// (wide), v103 = 127, v104 = -128, v105 = 1; temporaries v108 - v117; pairs: E = v[118:119] / v[106:107] entry {Rc | T << 16, Rb} (8-bit containers: {Rc | Rb << 8 | T << 16, Rb - Rc}) of the
 // two copies of the step,
 // W = v[120:121] ring words, R = v[122:123] record {A, N | C << 8 | B << 16}, M = v[124:125] {window beyond the prefix, u},
 // MM = v[126:127] = M << k (v127 = the mapped error).  s[92:93]: lanes whose N = RESET (or run mode); s[96:97]: lanes whose
@@ -37,10 +38,68 @@
 
 #define JLS_SDWA(s0, s1) " dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:" s0 " src1_sel:" s1 "\n"
 
-#define JLS_STEP_PROLOGUE                                                                                                          \
-    "s_mov_b64 s[98:99], exec\n"                                                                                                  \
-    "s_mov_b64 exec, %[inl]\n"                                                                                                    \
-    "ds_read_b64 v[118:119], %[pp] offset:8\n"                                                                                    \
+// MED relative to Ra, for samples in 8-bit containers (default on; -DJLS_STEP_MED_FROM_RA=0 for the A/B: every rendering then
+// has the text of the wide one).  median(Ra, Rb, Ra + Rb - Rc) = Ra + median(0, Rb - Ra, Rb - Rc): with the prepared entry
+// {Rc | Rb << 8 | T << 16, Rb - Rc} every reader of Ra in a step -- the Q3 difference, the two SDWA instructions of the predictor,
+// the one-byte store -- takes its low byte, and the lossless step of a MAXVAL = 255 scan leaves the sample unmasked: one
+// instruction less on the chain Ra -> Q3.  (VOP3 has no SDWA selects: v_med3 of the absolute form needs a clean Ra.)
+#ifndef JLS_STEP_MED_FROM_RA
+#define JLS_STEP_MED_FROM_RA 1
+#endif
+
+// The count of a call is a count of TRIPS (default on; -DJLS_STEP_TRIP_COUNT=0: a count of steps, tested behind every copy).
+// The exit test stands once per trip, behind the last copy, and its branch is the back edge: one conditional branch taken per
+// trip instead of a not-taken one per step and a taken s_branch.  A call of an odd number of steps enters the loop at copy "b"
+// (L_enterb loads that copy's entry pair), so a line's last sample -- one step -- is one trip.  The run service brings the count
+// down to whole trips from the copy it was called from (JLS_STEP_BUDGET_*), and leaves through L_doneb -- the state of a loop that
+// ended by count -- when a served scan may not even finish the trip.
+#ifndef JLS_STEP_TRIP_COUNT
+#define JLS_STEP_TRIP_COUNT 1
+#endif
+// lm and pp advance once per trip (default on; -DJLS_STEP_TRIP_POINTERS=0: once per step).  Copy "b" adds both steps of the trip;
+// copy "a" addresses through the offset fields of its DS instructions, so that between the place of a's advance and b's the true
+// pointers are lm + SZ and pp + 8.  Whatever leaves the loop from copy "a" adds that on its way (L_donea, JLS_STEP_RARE_ENTER_A), and
+// the run service works on true pointers and takes it off again when it returns into copy "a" (JLS_STEP_RARE_LEAVE_A).
+#ifndef JLS_STEP_TRIP_POINTERS
+#define JLS_STEP_TRIP_POINTERS 1
+#endif
+#if JLS_STEP_TRIP_POINTERS
+#define JLS_STEP_ADVANCE_A(SZ) ""
+#define JLS_STEP_ADVANCE_B(SZ) "v_add_u32 %[lm], 2 * " SZ ", %[lm]\n v_add_u32 %[pp], 16, %[pp]\n"
+#define JLS_STEP_STORE_OFFSET_A(SZ) " offset:" SZ
+#define JLS_STEP_NEXT_ENTRY_A "16"
+#define JLS_STEP_TRUE_UP_A(SZ) "v_add_u32 %[lm], " SZ ", %[lm]\n v_add_u32 %[pp], 8, %[pp]\n"
+#define JLS_STEP_RARE_ENTER_A(SZ) JLS_STEP_TRUE_UP_A(SZ)
+#define JLS_STEP_RARE_LEAVE_A(SZ) "v_add_u32 %[lm], -" SZ ", %[lm]\n v_add_u32 %[pp], -8, %[pp]\n"
+#else
+#define JLS_STEP_ADVANCE_A(SZ) "v_add_u32 %[lm], " SZ ", %[lm]\n v_add_u32 %[pp], 8, %[pp]\n"
+#define JLS_STEP_ADVANCE_B(SZ) JLS_STEP_ADVANCE_A(SZ)
+#define JLS_STEP_STORE_OFFSET_A(SZ) ""
+#define JLS_STEP_NEXT_ENTRY_A "8"
+#define JLS_STEP_TRUE_UP_A(SZ) ""
+#define JLS_STEP_RARE_ENTER_A(SZ) ""
+#define JLS_STEP_RARE_LEAVE_A(SZ) ""
+#endif
+// how a copy ends: PER_STEP -- the count test of a loop that counts steps (DONE: its exit, NEXT: what follows when the loop goes on);
+// with a count of trips copy "a" ends in nothing and copy "b" in the back edge
+#define JLS_STEP_TAIL_PER_STEP(DONE, NEXT) "s_sub_u32 %[cnt], %[cnt], 1\n s_cbranch_scc1 " DONE "%=\n" NEXT
+#if JLS_STEP_TRIP_COUNT
+#define JLS_STEP_TAIL_A ""
+#define JLS_STEP_TAIL_B "s_sub_u32 %[cnt], %[cnt], 1\n s_cbranch_scc0 L_stepa%=\n s_branch L_doneb%=\n"
+// v89 = samples a served scan may still take -> trips it may still take behind this one; s[86:87] (copy "a"): scans that may not
+// take the trip's second step
+#define JLS_STEP_BUDGET_A "v_cmp_eq_u32_e64 s[86:87], 0, v89\n v_add_u32 v89, -1, v89\n v_lshrrev_b32 v89, 1, v89\n"
+#define JLS_STEP_BUDGET_B "v_lshrrev_b32 v89, 1, v89\n"
+#define JLS_STEP_SHORT_A "s_cmp_lg_u64 s[86:87], 0\n s_cbranch_scc1 L_doneb%=\n"   /* (lm and pp are true here) */
+#else
+#define JLS_STEP_TAIL_A JLS_STEP_TAIL_PER_STEP("L_donea", "")
+#define JLS_STEP_TAIL_B JLS_STEP_TAIL_PER_STEP("L_doneb", "s_branch L_stepa%=\n")
+#define JLS_STEP_BUDGET_A ""
+#define JLS_STEP_BUDGET_B ""
+#define JLS_STEP_SHORT_A ""
+#endif
+
+#define JLS_STEP_PROLOGUE_CONSTANTS                                                                                                \
     "v_mov_b32 v100, 0xb60\n"                                                                                                     \
     "v_mov_b32 v101, 0x0c0c0400\n"                                                                                                \
     "v_mov_b32 v103, 0x7f\n"                                                                                                      \
@@ -49,22 +108,48 @@
     "v_mov_b32 v127, 0\n"                                                                                                         \
     "v_lshrrev_b32 v93, 16, %[cfg]\n"                                       /* RESET */                                          \
     "s_waitcnt lgkmcnt(0)\n"
+// a loop that counts steps: every call starts at copy "a"
+#define JLS_STEP_PROLOGUE_PER_STEP                                                                                                 \
+    "s_mov_b64 s[98:99], exec\n"                                                                                                  \
+    "s_mov_b64 exec, %[inl]\n"                                                                                                    \
+    "ds_read_b64 v[118:119], %[pp] offset:8\n"                                                                                    \
+    JLS_STEP_PROLOGUE_CONSTANTS
+#if JLS_STEP_TRIP_COUNT
+// cnt comes in as steps - 1: (steps - 1) >> 1 trips behind the first one, which is the second half of a trip when steps is odd
+#define JLS_STEP_PROLOGUE                                                                                                          \
+    "s_mov_b64 s[98:99], exec\n"                                                                                                  \
+    "s_mov_b64 exec, %[inl]\n"                                                                                                    \
+    "s_and_b32 s80, %[cnt], 1\n"                                                                                                  \
+    "s_lshr_b32 %[cnt], %[cnt], 1\n"                                                                                              \
+    "s_cmp_eq_u32 s80, 0\n"                                                                                                       \
+    "s_cbranch_scc1 L_enterb%=\n"                                                                                                 \
+    "ds_read_b64 v[118:119], %[pp] offset:8\n"                                                                                    \
+    JLS_STEP_PROLOGUE_CONSTANTS
+#define JLS_STEP_ENTER_B(SZ)                                                                                                       \
+    "L_enterb%=:\n"                                                                                                               \
+    "ds_read_b64 v[106:107], %[pp] offset:8\n"                                                                                    \
+    JLS_STEP_RARE_LEAVE_A(SZ)                                               /* (copy "b" advances by the whole trip) */          \
+    JLS_STEP_PROLOGUE_CONSTANTS                                                                                                    \
+    "s_branch L_stepb%=\n"
+#else
+#define JLS_STEP_PROLOGUE JLS_STEP_PROLOGUE_PER_STEP
+#define JLS_STEP_ENTER_B(SZ) ""
+#endif
 
 // The stores of a step: the previous step's record -- before this step's record is requested: it may be the same one -- and
 // the previous step's sample, which nobody reads before the loop is over: it goes behind the request of the record, off the
 // chain (LATE), or with the record (EARLY; the microbenchmark's comparison).  Both are issued by all lanes of a scan (the same
 // value to the same address): narrowing EXEC to one lane per scan around them costs more than it saves
 // (profiles/r06_steploop_v2_compositions.txt).
-#define JLS_STEP_STORES_LATE(ST) "ds_write2_b32 %[where], %[ua], v111 offset1:1\n", "2", ST " %[lm], %[a]\n", "1"
-#define JLS_STEP_STORES_EARLY(ST) "ds_write2_b32 %[where], %[ua], v111 offset1:1\n" ST " %[lm], %[a]\n", "3", "", "0"
+// (OFF: the offset field of the sample's store, JLS_STEP_STORE_OFFSET_A in copy "a")
+#define JLS_STEP_STORES_LATE(ST, OFF) "ds_write2_b32 %[where], %[ua], v111 offset1:1\n", "2", ST " %[lm], %[a]" OFF "\n", "1"
+#define JLS_STEP_STORES_EARLY(ST, OFF) "ds_write2_b32 %[where], %[ua], v111 offset1:1\n" ST " %[lm], %[a]" OFF "\n", "3", "", "0"
 
 // The part of a step between the request of Q3 and its arrival, in three pieces: the order in which they are issued is a
 // parameter (measured: tools/microbench/steploop.hip).
 #define JLS_STEP_COMMIT_AND_WINDOW(SZ, TOP_EXTRA) \
-    /* the previous step becomes final: bit position, line slot, entry */ \
+    /* the previous step becomes final: bit position, and (TOP_EXTRA begins with the copy's JLS_STEP_ADVANCE_*) line slot, entry */ \
     "v_add3_u32 %[p], %[p], %[u1], %[k]\n" \
-    "v_add_u32 %[lm], " SZ ", %[lm]\n" \
-    "v_add_u32 %[pp], 8, %[pp]\n" \
     TOP_EXTRA \
     "v_bfe_u32 v109, %[p], 5, 8\n" \
     "v_lshl_add_u32 v109, v109, 2, %[ring]\n" \
@@ -74,6 +159,11 @@
     "v_add_u32 v115, %[a], " E1 "\n" \
     "v_sub_u32_sdwa v115, v115, " E0 JLS_SDWA("DWORD", RC) \
     "v_med3_i32 v115, v115, %[a], " E1 "\n"
+// the same number from the entry {Rc | Rb << 8 | T << 16, Rb - Rc}: Ra + median(0, Rb - Ra, Rb - Rc), Ra by its low byte
+#define JLS_STEP_PREDICTOR_FROM_RA(RC, E0, E1) \
+    "v_sub_u32_sdwa v115, " E0 ", %[a]" JLS_SDWA("BYTE_1", "BYTE_0") \
+    "v_med3_i32 v115, v115, 0, " E1 "\n" \
+    "v_add_u32_sdwa v115, v115, %[a]" JLS_SDWA("DWORD", "BYTE_0")
 #define JLS_STEP_A13 \
     /* A.13 of the previous step: minus_delta = 1 - (tb > 0) - (tb + N' > 0), B' = med3(tb + minus_delta N', 1 - N', 0), C' */ \
     "v_med3_i32 v110, %[utb], 0, 1\n" \
@@ -108,6 +198,11 @@
     "v_mad_i32_i24 v115, v111, v116, v115\n"                                                                                      \
     "v_and_b32 %[a], %[smax], v115\n"
 #define JLS_STEP_LOSSLESS "", JLS_STEP_ODD_LOSSLESS, JLS_STEP_RECON_LOSSLESS, "v111"
+// MAXVAL = 255 with MED relative to Ra: the sample is the low byte of Px + sign Errval; nothing in the loop reads more of it, and
+// the code behind the loop gets it masked (JLS_STEP_EXIT_BYTE)
+#define JLS_STEP_RECON_LOSSLESS_BYTE "v_mad_i32_i24 %[a], v111, v116, v115\n"
+#define JLS_STEP_LOSSLESS_BYTE "", JLS_STEP_ODD_LOSSLESS, JLS_STEP_RECON_LOSSLESS_BYTE, "v111"
+#define JLS_STEP_EXIT_BYTE "v_and_b32 %[a], 0xff, %[a]\n"
 #define JLS_STEP_RECON_NEAR                                                                                                        \
     "v_mad_i32_i24 v115, v111, v117, v115\n"                                                                                      \
     "v_cmp_lt_i32 vcc, v115, v96\n"                                                                                               \
@@ -128,24 +223,26 @@
     "v_sub_u32 v97, %[smax], v96\n"                                                                                               \
     "v_sub_u32 v99, 0, v98\n"
 
-// One step.  SFX: label suffix of this copy; NEXT: what follows the step when the loop goes on ("" = the next copy).
-// RC: the half of the entry's first word that holds Rc ("BYTE_0" / "WORD_0"); SZ: bytes per sample; STORES: one of the above
+// One step.  SFX: label suffix of this copy; TAIL: how the copy ends (JLS_STEP_TAIL_*); NEXT_OFFSET: the offset field of the request of
+// the next entry ("8", JLS_STEP_NEXT_ENTRY_A in copy "a").
+// RC: the half of the entry's first word that holds Rc ("BYTE_0" / "WORD_0"); ASEL: what the Q3 difference reads of Ra ("BYTE_0"
+// with MED relative to Ra, else "DWORD"); PRED (an argument of ORDER): the predictor, JLS_STEP_PREDICTOR or _FROM_RA; SZ: bytes per sample; STORES: one of the above
 // (four arguments: the early stores, the LDS operations that may be outstanding when Q3 is awaited, the late store, those that
 // may be outstanding when the record is awaited);
 // Q3_ADDR: from v108 = Rc - Ra to the table index in v108 (8-bit: nothing, the constant goes into the offset field);
 // Q3_OFFSET: that offset; TOP_EXTRA / K_EXTRA / A_EXTRA: what wider samples add; KSEEN: the accumulation of k
 // (invoked from inside another macro with STORES as ONE argument there: it has become four by the time this one is looked at)
-#define JLS_STEP_BODY(SFX, NEXT, E0, E1, ENEXT, RC, SZ, BETWEEN, RING_WAIT, AFTER_REQUEST, EARLY_STORES, Q3_WAIT, LATE_STORE, RECORD_WAIT, Q3_ADDR, Q3_OFFSET, TOP_EXTRA, K_EXTRA, A_EXTRA, KSEEN, SIGN_EXTRA, ODD, RECON, UTB_SRC) \
+#define JLS_STEP_BODY(SFX, TAIL, E0, E1, ENEXT, NEXT_OFFSET, RC, ASEL, SZ, BETWEEN, RING_WAIT, AFTER_REQUEST, EARLY_STORES, Q3_WAIT, LATE_STORE, RECORD_WAIT, Q3_ADDR, Q3_OFFSET, TOP_EXTRA, K_EXTRA, A_EXTRA, KSEEN, SIGN_EXTRA, ODD, RECON, UTB_SRC) \
     "L_step" SFX "%=:\n"                                                                                                          \
     /* Q3: the one gradient that depends on the sample just decoded */                                                            \
-    "v_sub_u32_sdwa v108, " E0 ", %[a]" JLS_SDWA(RC, "DWORD")                                                                    \
+    "v_sub_u32_sdwa v108, " E0 ", %[a]" JLS_SDWA(RC, ASEL)                                                                       \
     Q3_ADDR                                                                                                                       \
     "ds_read_u8 v114, v108" Q3_OFFSET "\n"                                  /* LDS 1 */                                          \
     BETWEEN                                                                                                                       \
     EARLY_STORES                                                            /* LDS 3 (, 4) */                                    \
     "s_waitcnt lgkmcnt(" Q3_WAIT ")\n"                                      /* Q3 is here */                                     \
     "v_add_u32_sdwa %[qsu], v114, " E0 JLS_SDWA("DWORD", "WORD_1")                                                                \
-    "ds_read_b64 " ENEXT ", %[pp] offset:8\n"                               /* the next sample's entry, into the other copy's pair */ \
+    "ds_read_b64 " ENEXT ", %[pp] offset:" NEXT_OFFSET "\n"                 /* the next sample's entry, into the other copy's pair */ \
     "v_sad_u32 %[where], %[qsu], v100, %[recbase]\n"                                                                              \
     "ds_read_b64 v[122:123], %[where]\n"                                    /* the context record */                             \
     LATE_STORE                                                                                                                    \
@@ -187,9 +284,7 @@
     "s_or_b64 s[94:95], s[92:93], s[96:97]\n"                               /* anything rare in any lane? */                     \
     "s_cbranch_scc1 L_rare" SFX "%=\n"                                                                                            \
     "L_back" SFX "%=:\n"                                                                                                          \
-    "s_sub_u32 %[cnt], %[cnt], 1\n"                                                                                               \
-    "s_cbranch_scc1 L_done%=\n"                                             /* the steps of this call are done */                \
-    NEXT
+    TAIL                                                                    /* are the steps of this call done? */               \
 
 // What is rare: lanes of s[92:93] -- N had reached RESET: A + |Errval|, B + Errval and N are halved before N is incremented
 // (src/regular_mode_context.hpp:56-63; harmless in a lane whose "record" was record 0, which is run mode) -- and lanes that
@@ -208,7 +303,9 @@
 // line and entry pointers have moved on by the run and the entry of the sample behind the event is read again.  The loop's count
 // of steps is a count of SAMPLES per scan (the prepared entries reach 63 samples ahead, a line has an end): {entry address of the
 // call's first sample, samples left in the line} are at rctx + 32, a run that would take its scan beyond either is not served,
-// and the count shrinks to what the scan that is furthest ahead still has.  Whatever does not fit leaves the loop as before.
+// and the count shrinks to what the scan that is furthest ahead still has -- in whole trips, counted from the copy the service was
+// called from (BUDGET), and a scan that may not take the second step of the trip it was served in ends the loop as the count
+// does (SHORT).  ENTER / LEAVE: the half trip that copy "a" owes lm and pp.  Whatever does not fit leaves the loop as before.
 // (The C++ rendering of the loop in scan_group_decode.hip has the same service, statement by statement.)
 // LD / ST / SZ: load / store of a sample, bytes per sample; ENEXT: the entry pair of the NEXT step; WHICH: from Ra in v108 and
 // Rb in v109 to s[88:89] = the context of RItype 1; RECON: from the prediction in v112 and Errval (sign) in v114 to the sample
@@ -229,7 +326,7 @@
     "v_cndmask_b32_e64 v91, v91, v99, s[86:87]\n"                                                                                 \
     "v_add_u32 v112, v112, v91\n"                                                                                                 \
     "v_med3_i32 v112, v112, 0, %[smax]\n"
-#define JLS_STEP_RARE(SFX, LD, ST, SZ, ENEXT, WHICH, RECON)                                                                        \
+#define JLS_STEP_RARE(SFX, LD, ST, SZ, ENEXT, WHICH, RECON, ENTER, LEAVE, BUDGET, SHORT)                                                                      \
     "L_rare" SFX "%=:\n"                                                                                                          \
     "v_cndmask_b32_e64 v108, 0, 1, s[92:93]\n"                                                                                    \
     "v_and_b32 v109, 0xff, v123\n"                                                                                                \
@@ -240,6 +337,7 @@
     "v_add_u32 %[un1], 1, v109\n"                                                                                                 \
     "s_or_b64 %[fail], s[96:97], s[94:95]\n"                                                                                      \
     "s_cbranch_scc0 L_back" SFX "%=\n"                                      /* nothing but the halving */                        \
+    ENTER                                                                   /* lm and pp are true from here on */               \
     "s_cmp_lg_u64 s[96:97], 0\n"                                                                                                  \
     "s_cbranch_scc1 L_exit%=\n"                                             /* an unusual code somewhere: the loop ends anyway */ \
     /* -- every lane that stopped is in run mode */                                                                               \
@@ -392,6 +490,7 @@
     "v_sub_u32_e64 %[ri], v81, 1 clamp\n"                                   /* RUNindex - 1, not below 0 */                      \
     /* the count of steps left: no more than any served scan may still take */                                                    \
     "s_mov_b64 s[82:83], exec\n"                                                                                                  \
+    BUDGET                                                                                                                        \
     "L_budget" SFX "%=:\n"                                                                                                        \
     "s_ff1_i32_b64 s80, s[82:83]\n"                                                                                               \
     "s_nop 3\n"                                                            /* (a lane select written by the scalar unit) */     \
@@ -406,11 +505,15 @@
     "s_mov_b64 exec, s[90:91]\n"                                                                                                  \
     "s_mov_b64 %[fail], s[94:95]\n"                                                                                               \
     "s_cmp_lg_u64 s[94:95], 0\n"                                                                                                  \
-    "s_cbranch_scc0 L_back" SFX "%=\n"                                                                                            \
-    "s_branch L_exit%=\n"
+    "s_cbranch_scc1 L_exit%=\n"                                                                                                   \
+    SHORT                                                                   /* a served scan may not finish the trip */          \
+    LEAVE                                                                                                                         \
+    "s_branch L_back" SFX "%=\n"
 
-#define JLS_STEP_EPILOGUE(EXIT_EXTRA)                                                                                              \
-    "L_done%=:\n"                                                                                                                 \
+#define JLS_STEP_EPILOGUE(EXIT_EXTRA, TRUE_UP_A)                                                                                   \
+    "L_donea%=:\n"                                                          /* by count, out of copy "a" */                      \
+    TRUE_UP_A                                                                                                                     \
+    "L_doneb%=:\n"                                                                                                                 \
     "s_mov_b64 %[fail], 0\n"                                                                                                      \
     "L_exit%=:\n"                                                                                                                 \
     EXIT_EXTRA                                                                                                                    \
@@ -420,14 +523,14 @@
 // ORDER (three arguments): what is issued between the request of Q3 and its arrival, how many LDS operations may be outstanding
 // when the ring words are awaited, and what is issued right behind the request of the record.  WINDOW_FIRST: commit + bit-window request, predictor, A.13 (the record's store right in front of the
 // record request); UPDATE_FIRST: A.13 and the store first, so that the store has left the LDS queue when the record is requested.
-#define JLS_STEP_ORDER_WINDOW_FIRST(RC, SZ, TOP_EXTRA, E0, E1) JLS_STEP_COMMIT_AND_WINDOW(SZ, TOP_EXTRA) JLS_STEP_PREDICTOR(RC, E0, E1) JLS_STEP_A13, "4", ""
+#define JLS_STEP_ORDER_WINDOW_FIRST(PRED, RC, SZ, TOP_EXTRA, E0, E1) JLS_STEP_COMMIT_AND_WINDOW(SZ, TOP_EXTRA) PRED(RC, E0, E1) JLS_STEP_A13, "4", ""
 // PREDICTOR_LATE: the predictor -- which nothing needs before the reconstruction -- behind the request of the record, where the
 // wavefront would otherwise wait for it
-#define JLS_STEP_ORDER_PREDICTOR_LATE(RC, SZ, TOP_EXTRA, E0, E1) JLS_STEP_COMMIT_AND_WINDOW(SZ, TOP_EXTRA) JLS_STEP_A13, "4", JLS_STEP_PREDICTOR(RC, E0, E1)
-#define JLS_STEP_ORDER_UPDATE_FIRST(RC, SZ, TOP_EXTRA, E0, E1)                                                                     \
-    JLS_STEP_A13 "ds_write2_b32 %[where], %[ua], v111 offset1:1\n" JLS_STEP_COMMIT_AND_WINDOW(SZ, TOP_EXTRA) JLS_STEP_PREDICTOR(RC, E0, E1), "3", ""
+#define JLS_STEP_ORDER_PREDICTOR_LATE(PRED, RC, SZ, TOP_EXTRA, E0, E1) JLS_STEP_COMMIT_AND_WINDOW(SZ, TOP_EXTRA) JLS_STEP_A13, "4", PRED(RC, E0, E1)
+#define JLS_STEP_ORDER_UPDATE_FIRST(PRED, RC, SZ, TOP_EXTRA, E0, E1)                                                                    \
+    JLS_STEP_A13 "ds_write2_b32 %[where], %[ua], v111 offset1:1\n" JLS_STEP_COMMIT_AND_WINDOW(SZ, TOP_EXTRA) PRED(RC, E0, E1), "3", ""
 // (with UPDATE_FIRST the record's store is part of the order: the stores' macro then only has the sample)
-#define JLS_STEP_STORES_SAMPLE_LATE(ST) "", "2", ST " %[lm], %[a]\n", "1"
+#define JLS_STEP_STORES_SAMPLE_LATE(ST, OFF) "", "2", ST " %[lm], %[a]" OFF "\n", "1"
 #define JLS_STEP_KSEEN "v_or_b32 %[kseen], %[kseen], %[k]\n"
 
 // the loop: two steps per trip
@@ -435,15 +538,18 @@
 // (copy "a" works on the entry in v[118:119] and requests the next one into v[106:107], copy "b" the other way round: the entry of a
 // step stays valid to its end, so the predictor can sit behind the record request; the prologue loads the pair of copy "a", where
 // every call starts)
-#define JLS_STEP_LOOP_TEXT(RC, SZ, LD, ORDER, STORES, Q3_ADDR, Q3_OFFSET, TOP_EXTRA, K_EXTRA, A_EXTRA, EXIT_EXTRA, MODE, RARE_A, RARE_B)     \
+#define JLS_STEP_LOOP_TEXT(RC, ASEL, PRED, SZ, LD, ORDER, ST, Q3_ADDR, Q3_OFFSET, TOP_EXTRA, K_EXTRA, A_EXTRA, EXIT_EXTRA, MODE, RARE_A, RARE_B)     \
     JLS_STEP_PROLOGUE                                                                                                              \
-    JLS_STEP_BODY_X("a", "", "v118", "v119", "v[106:107]", RC, SZ, ORDER(RC, SZ, TOP_EXTRA, "v118", "v119"), STORES, Q3_ADDR, Q3_OFFSET, TOP_EXTRA, \
-                  K_EXTRA, A_EXTRA, JLS_STEP_KSEEN, MODE)                                                                          \
-    JLS_STEP_BODY_X("b", "s_branch L_stepa%=\n", "v106", "v107", "v[118:119]", RC, SZ, ORDER(RC, SZ, TOP_EXTRA, "v106", "v107"), STORES, Q3_ADDR, \
+    JLS_STEP_BODY_X("a", JLS_STEP_TAIL_A, "v118", "v119", "v[106:107]", JLS_STEP_NEXT_ENTRY_A, RC, ASEL, SZ,                      \
+                  ORDER(PRED, RC, SZ, JLS_STEP_ADVANCE_A(SZ) TOP_EXTRA, "v118", "v119"), JLS_STEP_STORES_LATE(ST, JLS_STEP_STORE_OFFSET_A(SZ)), \
+                  Q3_ADDR, Q3_OFFSET, TOP_EXTRA, K_EXTRA, A_EXTRA, JLS_STEP_KSEEN, MODE)                                           \
+    JLS_STEP_BODY_X("b", JLS_STEP_TAIL_B, "v106", "v107", "v[118:119]", "8", RC, ASEL, SZ,                                        \
+                  ORDER(PRED, RC, SZ, JLS_STEP_ADVANCE_B(SZ) TOP_EXTRA, "v106", "v107"), JLS_STEP_STORES_LATE(ST, ""), Q3_ADDR,    \
                   Q3_OFFSET, TOP_EXTRA, K_EXTRA, A_EXTRA, JLS_STEP_KSEEN, MODE)                                                    \
+    JLS_STEP_ENTER_B(SZ)                                                                                                           \
     RARE_A                                                                                                                         \
     RARE_B                                                                                                                         \
-    JLS_STEP_EPILOGUE(EXIT_EXTRA)
+    JLS_STEP_EPILOGUE(EXIT_EXTRA, JLS_STEP_TRUE_UP_A(SZ))
 
 #define JLS_STEP_LOOP_CLOBBERS                                                                                                     \
     "memory", "vcc", "scc", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96",   \
@@ -452,8 +558,11 @@
         "v125", "v126", "v127"
 
 // the rare path of the four renderings (8-bit / wider samples, lossless / near-lossless), for the two copies of the step
-#define JLS_STEP_RARE_NARROW(SFX, ENEXT, WHICH, RECON) JLS_STEP_RARE(SFX, "ds_read_u8", "ds_write_b8", "1", ENEXT, WHICH, RECON)
-#define JLS_STEP_RARE_WIDE(SFX, ENEXT, WHICH, RECON) JLS_STEP_RARE(SFX, "ds_read_u16", "ds_write_b16", "2", ENEXT, WHICH, RECON)
+#define JLS_STEP_RARE_A(LD, ST, SZ, WHICH, RECON)                                                                                 \
+    JLS_STEP_RARE("a", LD, ST, SZ, "v[106:107]", WHICH, RECON, JLS_STEP_RARE_ENTER_A(SZ), JLS_STEP_RARE_LEAVE_A(SZ), JLS_STEP_BUDGET_A, JLS_STEP_SHORT_A)
+#define JLS_STEP_RARE_B(LD, ST, SZ, WHICH, RECON) JLS_STEP_RARE("b", LD, ST, SZ, "v[118:119]", WHICH, RECON, "", "", JLS_STEP_BUDGET_B, "")
+#define JLS_STEP_RARE_NARROW(SFX, WHICH, RECON) JLS_STEP_RARE_##SFX("ds_read_u8", "ds_write_b8", "1", WHICH, RECON)
+#define JLS_STEP_RARE_WIDE(SFX, WHICH, RECON) JLS_STEP_RARE_##SFX("ds_read_u16", "ds_write_b16", "2", WHICH, RECON)
 // cfg: escape_base | qbpp << 8 | RESET << 16 (escape_base: an event's escape prefix is escape_base - J); gl: lanes per scan
 #define JLS_STEP_OPERANDS_OUT                                                                                                      \
     [a] "+v"(a), [p] "+v"(p), [lm] "+v"(lm), [pp] "+v"(pp), [where] "+v"(where), [ua] "+v"(u_a), [un1] "+v"(u_n1), [utb] "+v"(u_tb), \
@@ -464,13 +573,42 @@
     [ring] "v"(ring_address), [recbase] "v"(records_address), [limitv] "v"(limit_v), [cfg] "v"(cfg_v), [inl] "s"(in_line_m),       \
         [smax] "s"(maxval_s), [rctx] "v"(run_ctx_address), [gl] "n"(G)
 
-#define JLS_STEP_LOOP_ASM_NARROW()                                                                                                 \
-    asm volatile(JLS_STEP_LOOP_TEXT("BYTE_0", "1", "ds_read_u8", JLS_STEP_ORDER_WINDOW_FIRST,                                      \
-                                    JLS_STEP_STORES_LATE("ds_write_b8"), "", " offset:255", "", "", "", "", JLS_STEP_LOSSLESS,      \
-                                    JLS_STEP_RARE_NARROW("a", "v[106:107]", JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS), JLS_STEP_RARE_NARROW("b", "v[118:119]", JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS))                          \
+// 8-bit containers: how a step reads Ra, and its predictor (JLS_STEP_MED_FROM_RA)
+#if JLS_STEP_MED_FROM_RA
+#define JLS_STEP_NARROW_ASEL "BYTE_0"
+#define JLS_STEP_NARROW_PRED JLS_STEP_PREDICTOR_FROM_RA
+#else
+#define JLS_STEP_NARROW_ASEL "DWORD"
+#define JLS_STEP_NARROW_PRED JLS_STEP_PREDICTOR
+#endif
+#define JLS_STEP_LOOP_ASM_NARROW_MASKED()                                                                                          \
+    asm volatile(JLS_STEP_LOOP_TEXT("BYTE_0", JLS_STEP_NARROW_ASEL, JLS_STEP_NARROW_PRED, "1", "ds_read_u8", JLS_STEP_ORDER_WINDOW_FIRST, \
+                                    "ds_write_b8", "", " offset:255", "", "", "", "", JLS_STEP_LOSSLESS,      \
+                                    JLS_STEP_RARE_NARROW(A, JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS), JLS_STEP_RARE_NARROW(B, JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS))                          \
                  : JLS_STEP_OPERANDS_OUT                                                                                           \
                  : JLS_STEP_OPERANDS_IN                                                                                            \
                  : JLS_STEP_LOOP_CLOBBERS)
+#if JLS_STEP_MED_FROM_RA
+// two texts in one kernel, chosen by the wave-uniform MAXVAL: 255 -- the sample stays unmasked inside the loop -- and the scans
+// of 2 - 7 bits, which keep the mask
+#define JLS_STEP_LOOP_ASM_NARROW()                                                                                                 \
+    do                                                                                                                             \
+    {                                                                                                                              \
+        if (maxval_s == 255)                                                                                                       \
+            asm volatile(JLS_STEP_LOOP_TEXT("BYTE_0", "BYTE_0", JLS_STEP_PREDICTOR_FROM_RA, "1", "ds_read_u8", JLS_STEP_ORDER_WINDOW_FIRST, \
+                                            "ds_write_b8", "", " offset:255", "", "", "", JLS_STEP_EXIT_BYTE, \
+                                            JLS_STEP_LOSSLESS_BYTE,                                                                \
+                                            JLS_STEP_RARE_NARROW(A, JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS), \
+                                            JLS_STEP_RARE_NARROW(B, JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS)) \
+                         : JLS_STEP_OPERANDS_OUT                                                                                   \
+                         : JLS_STEP_OPERANDS_IN                                                                                    \
+                         : JLS_STEP_LOOP_CLOBBERS);                                                                                \
+        else                                                                                                                       \
+            JLS_STEP_LOOP_ASM_NARROW_MASKED();                                                                                     \
+    } while (0)
+#else
+#define JLS_STEP_LOOP_ASM_NARROW() JLS_STEP_LOOP_ASM_NARROW_MASKED()
+#endif
 
 // wider samples: the difference is clamped to the table (-cap .. cap, cap = T3) and the table index needs its base added; the
 // mapped error of a FINISHED step is accumulated (|Errval| > 65535 is invalid data), so is every updated A (2^24), and a
@@ -482,10 +620,10 @@
 #define JLS_STEP_WIDE_Q3 "v_med3_i32 v108, v108, v102, %[vcap]\n v_add_u32 v108, %[vcap], v108\n"
 #define JLS_STEP_LOOP_ASM_WIDE()                                                                                                   \
     asm volatile("v_sub_u32 v102, 0, %[vcap]\n"                                                                                   \
-                 JLS_STEP_LOOP_TEXT("WORD_0", "2", "ds_read_u16", JLS_STEP_ORDER_WINDOW_FIRST, JLS_STEP_STORES_LATE("ds_write_b16"), \
+                 JLS_STEP_LOOP_TEXT("WORD_0", "DWORD", JLS_STEP_PREDICTOR, "2", "ds_read_u16", JLS_STEP_ORDER_WINDOW_FIRST, "ds_write_b16", \
                                     JLS_STEP_WIDE_Q3, "", JLS_STEP_CHECKED_TOP, JLS_STEP_CHECKED_K, JLS_STEP_CHECKED_A,             \
                                     JLS_STEP_CHECKED_EXIT, JLS_STEP_LOSSLESS,                                                      \
-                                    JLS_STEP_RARE_WIDE("a", "v[106:107]", JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS), JLS_STEP_RARE_WIDE("b", "v[118:119]", JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS))                            \
+                                    JLS_STEP_RARE_WIDE(A, JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS), JLS_STEP_RARE_WIDE(B, JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS))                            \
                  : JLS_STEP_OPERANDS_OUT JLS_STEP_OPERANDS_CHECKED                                                                 \
                  : JLS_STEP_OPERANDS_IN, [vcap] "v"(cap_v)                                                                         \
                  : JLS_STEP_LOOP_CLOBBERS)
@@ -494,17 +632,17 @@
 // qbpp is small; |Errval| and A are bounded by the same rules).  nr: NEAR | RANGE (2 NEAR + 1) << 8.
 #define JLS_STEP_LOOP_ASM_NARROW_NEAR()                                                                                            \
     asm volatile(JLS_STEP_NEAR_CONSTANTS                                                                                           \
-                 JLS_STEP_LOOP_TEXT("BYTE_0", "1", "ds_read_u8", JLS_STEP_ORDER_WINDOW_FIRST, JLS_STEP_STORES_LATE("ds_write_b8"), \
+                 JLS_STEP_LOOP_TEXT("BYTE_0", JLS_STEP_NARROW_ASEL, JLS_STEP_NARROW_PRED, "1", "ds_read_u8", JLS_STEP_ORDER_WINDOW_FIRST, "ds_write_b8", \
                                     "", " offset:255", JLS_STEP_CHECKED_TOP, JLS_STEP_CHECKED_K, JLS_STEP_CHECKED_A,                \
-                                    JLS_STEP_CHECKED_EXIT, JLS_STEP_NEAR, JLS_STEP_RARE_NARROW("a", "v[106:107]", JLS_RUN_WHICH_NEAR, JLS_RUN_RECON_NEAR), JLS_STEP_RARE_NARROW("b", "v[118:119]", JLS_RUN_WHICH_NEAR, JLS_RUN_RECON_NEAR)) \
+                                    JLS_STEP_CHECKED_EXIT, JLS_STEP_NEAR, JLS_STEP_RARE_NARROW(A, JLS_RUN_WHICH_NEAR, JLS_RUN_RECON_NEAR), JLS_STEP_RARE_NARROW(B, JLS_RUN_WHICH_NEAR, JLS_RUN_RECON_NEAR)) \
                  : JLS_STEP_OPERANDS_OUT JLS_STEP_OPERANDS_CHECKED                                                                 \
                  : JLS_STEP_OPERANDS_IN, [nr] "s"(near_range_s)                                                                    \
                  : JLS_STEP_LOOP_CLOBBERS)
 #define JLS_STEP_LOOP_ASM_WIDE_NEAR()                                                                                              \
     asm volatile("v_sub_u32 v102, 0, %[vcap]\n" JLS_STEP_NEAR_CONSTANTS                                                           \
-                 JLS_STEP_LOOP_TEXT("WORD_0", "2", "ds_read_u16", JLS_STEP_ORDER_WINDOW_FIRST, JLS_STEP_STORES_LATE("ds_write_b16"), \
+                 JLS_STEP_LOOP_TEXT("WORD_0", "DWORD", JLS_STEP_PREDICTOR, "2", "ds_read_u16", JLS_STEP_ORDER_WINDOW_FIRST, "ds_write_b16", \
                                     JLS_STEP_WIDE_Q3, "", JLS_STEP_CHECKED_TOP, JLS_STEP_CHECKED_K, JLS_STEP_CHECKED_A,             \
-                                    JLS_STEP_CHECKED_EXIT, JLS_STEP_NEAR, JLS_STEP_RARE_WIDE("a", "v[106:107]", JLS_RUN_WHICH_NEAR, JLS_RUN_RECON_NEAR), JLS_STEP_RARE_WIDE("b", "v[118:119]", JLS_RUN_WHICH_NEAR, JLS_RUN_RECON_NEAR)) \
+                                    JLS_STEP_CHECKED_EXIT, JLS_STEP_NEAR, JLS_STEP_RARE_WIDE(A, JLS_RUN_WHICH_NEAR, JLS_RUN_RECON_NEAR), JLS_STEP_RARE_WIDE(B, JLS_RUN_WHICH_NEAR, JLS_RUN_RECON_NEAR)) \
                  : JLS_STEP_OPERANDS_OUT JLS_STEP_OPERANDS_CHECKED                                                                 \
                  : JLS_STEP_OPERANDS_IN, [vcap] "v"(cap_v), [nr] "s"(near_range_s)                                                 \
                  : JLS_STEP_LOOP_CLOBBERS)

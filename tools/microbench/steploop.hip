@@ -17,38 +17,73 @@
 #define WINDOW_FIRST JLS_STEP_ORDER_WINDOW_FIRST
 #define UPDATE_FIRST JLS_STEP_ORDER_UPDATE_FIRST
 #define PREDICTOR_LATE JLS_STEP_ORDER_PREDICTOR_LATE
+// The compositions of rounds 6 - 23 count steps and advance lm and pp in every step, whatever the product's switches are:
+// they are written with the pieces that do not depend on them.
+#define ADVANCE "v_add_u32 %[lm], 1, %[lm]\n v_add_u32 %[pp], 8, %[pp]\n"
+#define RARE(SFX, ENEXT)                                                                                                          \
+    JLS_STEP_RARE(SFX, "ds_read_u8", "ds_write_b8", "1", ENEXT, JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS, "", "", "", "")
+// ASEL, PRED, EXIT, MODE: how a step reads Ra, its predictor, what follows the loop and its reconstruction ("DWORD",
+// JLS_STEP_PREDICTOR, "", JLS_STEP_LOSSLESS: the text of wider samples and of -DJLS_STEP_MED_FROM_RA=0)
 // one step per trip: the one copy requests the next entry into its own pair (the predictor has to come before the request)
-#define RARE(SFX, ENEXT) JLS_STEP_RARE(SFX, "ds_read_u8", "ds_write_b8", "1", ENEXT, JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS)
-#define LOOP1(ORDER, STORES, KSEEN)                                                                                               \
-    JLS_STEP_PROLOGUE JLS_STEP_BODY_X("a", "s_branch L_stepa%=\n", "v118", "v119", "v[118:119]", "BYTE_0", "1",                   \
-                                      ORDER("BYTE_0", "1", "", "v118", "v119"), STORES, "", " offset:255", "", "", "", KSEEN,       \
-                                      JLS_STEP_LOSSLESS)                                                                           \
-        RARE("a", "v[118:119]") JLS_STEP_EPILOGUE("")
-#define LOOP2(ORDER, STORES, KSEEN)                                                                                               \
-    JLS_STEP_PROLOGUE JLS_STEP_BODY_X("a", "", "v118", "v119", "v[106:107]", "BYTE_0", "1", ORDER("BYTE_0", "1", "", "v118", "v119"), \
-                                      STORES, "", " offset:255", "", "", "", KSEEN, JLS_STEP_LOSSLESS)                              \
-        JLS_STEP_BODY_X("b", "s_branch L_stepa%=\n", "v106", "v107", "v[118:119]", "BYTE_0", "1",                                  \
-                        ORDER("BYTE_0", "1", "", "v106", "v107"), STORES, "", " offset:255", "", "", "", KSEEN, JLS_STEP_LOSSLESS)   \
-            RARE("a", "v[106:107]") RARE("b", "v[118:119]") JLS_STEP_EPILOGUE("")
+#define LOOP1(ORDER, STORES, KSEEN, ASEL, PRED, EXIT, MODE)                                                                       \
+    JLS_STEP_PROLOGUE_PER_STEP                                                                                                     \
+    JLS_STEP_BODY_X("a", JLS_STEP_TAIL_PER_STEP("L_doneb", "s_branch L_stepa%=\n"), "v118", "v119", "v[118:119]", "8", "BYTE_0", ASEL, "1", \
+                    ORDER(PRED, "BYTE_0", "1", ADVANCE, "v118", "v119"), STORES, "", " offset:255", "", "", "", KSEEN, MODE)        \
+        RARE("a", "v[118:119]") JLS_STEP_EPILOGUE(EXIT, "")
+#define LOOP2(ORDER, STORES, KSEEN, ASEL, PRED, EXIT, MODE)                                                                       \
+    JLS_STEP_PROLOGUE_PER_STEP                                                                                                     \
+    JLS_STEP_BODY_X("a", JLS_STEP_TAIL_PER_STEP("L_donea", ""), "v118", "v119", "v[106:107]", "8", "BYTE_0", ASEL, "1",            \
+                    ORDER(PRED, "BYTE_0", "1", ADVANCE, "v118", "v119"), STORES, "", " offset:255", "", "", "", KSEEN, MODE)        \
+        JLS_STEP_BODY_X("b", JLS_STEP_TAIL_PER_STEP("L_doneb", "s_branch L_stepa%=\n"), "v106", "v107", "v[118:119]", "8", "BYTE_0", ASEL, "1", \
+                        ORDER(PRED, "BYTE_0", "1", ADVANCE, "v106", "v107"), STORES, "", " offset:255", "", "", "", KSEEN, MODE)    \
+            RARE("a", "v[106:107]") RARE("b", "v[118:119]") JLS_STEP_EPILOGUE(EXIT, "")
+// the product's text as this file was compiled (-DJLS_STEP_TRIP_COUNT=0 / -DJLS_STEP_TRIP_POINTERS=0 / -DJLS_STEP_MED_FROM_RA=0)
+// (written out per variant below: a macro around JLS_STEP_LOOP_TEXT would expand MODE into its four arguments too early)
+#define PRODUCT_RARE_A JLS_STEP_RARE_NARROW(A, JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS)
+#define PRODUCT_RARE_B JLS_STEP_RARE_NARROW(B, JLS_RUN_WHICH_LOSSLESS, JLS_RUN_RECON_LOSSLESS)
+#define STR_(x) #x
+#define STR(x) STR_(x)
+#define SWITCHES " (trip count " STR(JLS_STEP_TRIP_COUNT) ", trip pointers " STR(JLS_STEP_TRIP_POINTERS) ", MED from Ra " STR(JLS_STEP_MED_FROM_RA) ")"
 #define NO_STORES "", "1", "", "0"
 
 #define STEPLOOP_NAME_0 "one step per trip, both stores early"
-#define STEPLOOP_TEXT_0 LOOP1(WINDOW_FIRST, JLS_STEP_STORES_EARLY("ds_write_b8"), JLS_STEP_KSEEN)
+#define STEPLOOP_TEXT_0 LOOP1(WINDOW_FIRST, JLS_STEP_STORES_EARLY("ds_write_b8", ""), JLS_STEP_KSEEN, "DWORD", JLS_STEP_PREDICTOR, "", JLS_STEP_LOSSLESS)
 #define STEPLOOP_NAME_1 "one step per trip, sample store late"
-#define STEPLOOP_TEXT_1 LOOP1(WINDOW_FIRST, JLS_STEP_STORES_LATE("ds_write_b8"), JLS_STEP_KSEEN)
+#define STEPLOOP_TEXT_1 LOOP1(WINDOW_FIRST, JLS_STEP_STORES_LATE("ds_write_b8", ""), JLS_STEP_KSEEN, "DWORD", JLS_STEP_PREDICTOR, "", JLS_STEP_LOSSLESS)
 #define STEPLOOP_NAME_2 "two steps per trip, both stores early"
-#define STEPLOOP_TEXT_2 LOOP2(WINDOW_FIRST, JLS_STEP_STORES_EARLY("ds_write_b8"), JLS_STEP_KSEEN)
-#define STEPLOOP_NAME_3 "PRODUCT: two steps per trip, sample late"
-#define STEPLOOP_TEXT_3 LOOP2(WINDOW_FIRST, JLS_STEP_STORES_LATE("ds_write_b8"), JLS_STEP_KSEEN)
+#define STEPLOOP_TEXT_2 LOOP2(WINDOW_FIRST, JLS_STEP_STORES_EARLY("ds_write_b8", ""), JLS_STEP_KSEEN, "DWORD", JLS_STEP_PREDICTOR, "", JLS_STEP_LOSSLESS)
+#define STEPLOOP_NAME_3 "round 6 .. 23: two steps per trip, sample late"
+#define STEPLOOP_TEXT_3 LOOP2(WINDOW_FIRST, JLS_STEP_STORES_LATE("ds_write_b8", ""), JLS_STEP_KSEEN, "DWORD", JLS_STEP_PREDICTOR, "", JLS_STEP_LOSSLESS)
 #define STEPLOOP_NAME_4 "product without k_seen"
-#define STEPLOOP_TEXT_4 LOOP2(WINDOW_FIRST, JLS_STEP_STORES_LATE("ds_write_b8"), "")
+#define STEPLOOP_TEXT_4 LOOP2(WINDOW_FIRST, JLS_STEP_STORES_LATE("ds_write_b8", ""), "", "DWORD", JLS_STEP_PREDICTOR, "", JLS_STEP_LOSSLESS)
 #define STEPLOOP_NAME_5 "product without the two stores"
-#define STEPLOOP_TEXT_5 LOOP2(WINDOW_FIRST, NO_STORES, JLS_STEP_KSEEN)
+#define STEPLOOP_TEXT_5 LOOP2(WINDOW_FIRST, NO_STORES, JLS_STEP_KSEEN, "DWORD", JLS_STEP_PREDICTOR, "", JLS_STEP_LOSSLESS)
 #define STEPLOOP_NAME_6 "A.13 and the record store first"
-#define STEPLOOP_TEXT_6 LOOP2(UPDATE_FIRST, JLS_STEP_STORES_SAMPLE_LATE("ds_write_b8"), JLS_STEP_KSEEN)
+#define STEPLOOP_TEXT_6 LOOP2(UPDATE_FIRST, JLS_STEP_STORES_SAMPLE_LATE("ds_write_b8", ""), JLS_STEP_KSEEN, "DWORD", JLS_STEP_PREDICTOR, "", JLS_STEP_LOSSLESS)
 #define STEPLOOP_NAME_7 "predictor behind the record request"
-#define STEPLOOP_TEXT_7 LOOP2(PREDICTOR_LATE, JLS_STEP_STORES_LATE("ds_write_b8"), JLS_STEP_KSEEN)
-#define STEPLOOP_VARIANTS 8
+#define STEPLOOP_TEXT_7 LOOP2(PREDICTOR_LATE, JLS_STEP_STORES_LATE("ds_write_b8", ""), JLS_STEP_KSEEN, "DWORD", JLS_STEP_PREDICTOR, "", JLS_STEP_LOSSLESS)
+#define STEPLOOP_NAME_8 "round 6 .. 23 with MED relative to Ra, sample masked"
+#define STEPLOOP_TEXT_8 LOOP2(WINDOW_FIRST, JLS_STEP_STORES_LATE("ds_write_b8", ""), JLS_STEP_KSEEN, "BYTE_0", JLS_STEP_PREDICTOR_FROM_RA, "", JLS_STEP_LOSSLESS)
+#define STEPLOOP_NAME_9 "round 6 .. 23 with MED relative to Ra, no mask"
+#define STEPLOOP_TEXT_9 LOOP2(WINDOW_FIRST, JLS_STEP_STORES_LATE("ds_write_b8", ""), JLS_STEP_KSEEN, "BYTE_0", JLS_STEP_PREDICTOR_FROM_RA, JLS_STEP_EXIT_BYTE,  \
+                              JLS_STEP_LOSSLESS_BYTE)
+#define STEPLOOP_NAME_10 "PRODUCT, MAXVAL = 255" SWITCHES
+#define STEPLOOP_NAME_11 "PRODUCT, MAXVAL < 255" SWITCHES
+#define PRODUCT_MASKED(ASEL, PRED)                                                                                                \
+    JLS_STEP_LOOP_TEXT("BYTE_0", ASEL, PRED, "1", "ds_read_u8", WINDOW_FIRST, "ds_write_b8", "", " offset:255", "", "", "", "",     \
+                       JLS_STEP_LOSSLESS, PRODUCT_RARE_A, PRODUCT_RARE_B)
+#if JLS_STEP_MED_FROM_RA
+#define STEPLOOP_TEXT_10                                                                                                          \
+    JLS_STEP_LOOP_TEXT("BYTE_0", "BYTE_0", JLS_STEP_PREDICTOR_FROM_RA, "1", "ds_read_u8", WINDOW_FIRST, "ds_write_b8", "", " offset:255", "", "", \
+                       "", JLS_STEP_EXIT_BYTE, JLS_STEP_LOSSLESS_BYTE, PRODUCT_RARE_A, PRODUCT_RARE_B)
+#define STEPLOOP_TEXT_11 PRODUCT_MASKED("BYTE_0", JLS_STEP_PREDICTOR_FROM_RA)
+#else
+#define STEPLOOP_TEXT_10 PRODUCT_MASKED("DWORD", JLS_STEP_PREDICTOR)
+#define STEPLOOP_TEXT_11 PRODUCT_MASKED("DWORD", JLS_STEP_PREDICTOR)
+#endif
+#define STEPLOOP_VARIANTS 12
+// the prepared entries of a variant: {Rc | T << 16, Rb}, or {Rc | Rb << 8 | T << 16, Rb - Rc}
+#define STEPLOOP_RELATIVE(V) ((V) == 8 || (V) == 9 || ((V) >= 10 && JLS_STEP_MED_FROM_RA))
 
 constexpr uint32_t kRegion = 9744, kRecords = 0, kRun = 2928, kRing = 2976, kPrep = 4008, kLine = 5584, kLut = 512;
 constexpr int kBurst = 60;
@@ -92,8 +127,9 @@ __device__ int quantize(int d)
         for (int e = sub; e < 192; e += 16)                                                                                       \
         {                                                                                                                         \
             const uint32_t q1 = (e % 2) ? 24 : 40, q2 = 24 + 8 * (uint32_t)((e / 2) % 3); /* never the run-mode context */        \
-            prep[2 * e] = (100u + (uint32_t)(e % 3)) | ((9u * (9u * q1 + q2)) << 16);                                             \
-            prep[2 * e + 1] = 101;                                                                                                \
+            const uint32_t rc = 100u + (uint32_t)(e % 3), rb = 101;                                                               \
+            prep[2 * e] = rc | (STEPLOOP_RELATIVE(V) ? rb << 8 : 0u) | ((9u * (9u * q1 + q2)) << 16);                             \
+            prep[2 * e + 1] = STEPLOOP_RELATIVE(V) ? rb - rc : rb;                                                                \
         }                                                                                                                         \
         __syncthreads();                                                                                                          \
         const uint32_t ring_address = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(region + kRing);             \
@@ -133,8 +169,8 @@ __device__ int quantize(int d)
         sink[threadIdx.x] = (uint32_t)a + p + k_seen + qsu8 + win_now + (uint32_t)u_a;                                            \
     }
 
-KERNEL(0) KERNEL(1) KERNEL(2) KERNEL(3) KERNEL(4) KERNEL(5) KERNEL(6) KERNEL(7)
-static_assert(STEPLOOP_VARIANTS == 8, "one KERNEL() per variant");
+KERNEL(0) KERNEL(1) KERNEL(2) KERNEL(3) KERNEL(4) KERNEL(5) KERNEL(6) KERNEL(7) KERNEL(8) KERNEL(9) KERNEL(10) KERNEL(11)
+static_assert(STEPLOOP_VARIANTS == 12, "one KERNEL() per variant");
 
 typedef void (*Kernel)(uint64_t*, uint32_t*, int);
 
@@ -142,9 +178,10 @@ int main(int argc, char** argv)
 {
     const int groups = argc > 1 ? atoi(argv[1]) : 256;
     const int repeats = 2000;
-    const Kernel kernels[] = {steploop_0, steploop_1, steploop_2, steploop_3, steploop_4, steploop_5, steploop_6, steploop_7};
+    const Kernel kernels[] = {steploop_0, steploop_1, steploop_2, steploop_3, steploop_4, steploop_5, steploop_6, steploop_7,
+                              steploop_8, steploop_9, steploop_10, steploop_11};
     const char* names[] = {STEPLOOP_NAME_0, STEPLOOP_NAME_1, STEPLOOP_NAME_2, STEPLOOP_NAME_3, STEPLOOP_NAME_4, STEPLOOP_NAME_5, STEPLOOP_NAME_6,
-                           STEPLOOP_NAME_7};
+                           STEPLOOP_NAME_7, STEPLOOP_NAME_8, STEPLOOP_NAME_9, STEPLOOP_NAME_10, STEPLOOP_NAME_11};
     uint64_t* d_out;
     uint32_t* d_sink;
     (void)hipMalloc(&d_out, sizeof(uint64_t) * 2 * 4 * groups);
@@ -152,7 +189,7 @@ int main(int argc, char** argv)
     const size_t lds = kLut + 16 * kRegion;
     printf("step loop alone: %d workgroups of 4 wavefronts (one per SIMD), 4 scans per wavefront, %zu bytes of LDS, %d bursts of %d steps\n",
            groups, lds, repeats, kBurst);
-    printf("%-44s %12s %12s %12s %s\n", "variant", "cyc/step min", "median", "max", "lanes that stopped");
+    printf("%-64s %12s %12s %12s %s\n", "variant", "cyc/step min", "median", "max", "lanes that stopped");
     for (int v = 0; v < STEPLOOP_VARIANTS; ++v)
     {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[v]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -178,7 +215,7 @@ int main(int argc, char** argv)
         if (per.empty())
             continue;
         std::sort(per.begin(), per.end());
-        printf("%-44s %12.1f %12.1f %12.1f %016llx\n", names[v], per.front(), per[per.size() / 2], per.back(), failed);
+        printf("%-64s %12.1f %12.1f %12.1f %016llx\n", names[v], per.front(), per[per.size() / 2], per.back(), failed);
     }
     return 0;
 }
