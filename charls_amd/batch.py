@@ -184,6 +184,11 @@ def _bind(lib):
         l.charls_amd_index_batch_host.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p, C.c_uint32, C.c_void_p, C.c_size_t, u64p,
                                                   C.POINTER(CodecParams), i32p]
         l.charls_amd_index_batch_host.restype = C.c_int32
+    if hasattr(l, "charls_amd_decode_rows_batch_device_ragged_markers"):  # (part 2m; an A/B tool may load a build from before it)
+        l.charls_amd_decode_rows_batch_device_ragged_markers.argtypes = l.charls_amd_decode_rows_batch_device_ragged.argtypes
+        l.charls_amd_decode_rows_batch_device_ragged_markers.restype = C.c_int32
+        l.charls_amd_band_marker_counters.argtypes = [u64p, C.c_int32]
+        l.charls_amd_band_marker_counters.restype = C.c_int32
     l._batch_bound = True
     return l
 
@@ -1259,6 +1264,20 @@ def decode_rows_batch_ragged(packed, offsets, sizes, indexes, first_rows, row_co
     """charls_amd_decode_rows_batch_device_ragged: rows [first_rows[f], first_rows[f] + row_counts[f]) of frame f of the packed
     streams into bands[f], a device tensor of its own (decode_rows' layout), through the frame's index where indexes[f] is
     one, from the top otherwise.  Returns errcs."""
+    return _decode_rows_ragged("charls_amd_decode_rows_batch_device_ragged", packed, offsets, sizes, indexes, first_rows, row_counts, bands,
+                               strides, capacities, lib)
+
+
+def decode_rows_batch_ragged_markers(packed, offsets, sizes, indexes, first_rows, row_counts, bands, *, strides=None, capacities=None,
+                                     lib=None):
+    """charls_amd_decode_rows_batch_device_ragged_markers (part 2m): decode_rows_batch_ragged, with the frames that have restart
+    intervals -- and no seek points -- decoded through their restart markers: only the intervals the band meets, all frames'
+    in one launch.  Bands and errcs are those of decode_rows_batch_ragged on a stream that decodes whole.  Returns errcs."""
+    return _decode_rows_ragged("charls_amd_decode_rows_batch_device_ragged_markers", packed, offsets, sizes, indexes, first_rows, row_counts,
+                               bands, strides, capacities, lib)
+
+
+def _decode_rows_ragged(name, packed, offsets, sizes, indexes, first_rows, row_counts, bands, strides, capacities, lib):
     import torch
     lib = lib or capi.load_product()
     l = _bind(lib)
@@ -1272,12 +1291,11 @@ def decode_rows_batch_ragged(packed, offsets, sizes, indexes, first_rows, row_co
     errcs = np.zeros(count, dtype=np.int32)
     u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
     stream = torch.cuda.current_stream(packed.device).cuda_stream
-    rc = l.charls_amd_decode_rows_batch_device_ragged(count, packed.data_ptr(), offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p),
-                                                      table.ctypes.data, pitch, index_sizes.ctypes.data_as(u64p), first_rows.ctypes.data_as(u32p),
-                                                      row_counts.ctypes.data_as(u32p), dests, errcs.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                      C.c_void_p(stream))
+    rc = getattr(l, name)(count, packed.data_ptr(), offsets.ctypes.data_as(u64p), sizes.ctypes.data_as(u64p), table.ctypes.data, pitch,
+                          index_sizes.ctypes.data_as(u64p), first_rows.ctypes.data_as(u32p), row_counts.ctypes.data_as(u32p), dests,
+                          errcs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream))
     if rc != 0:
-        raise capi.JpegLSError(rc, "charls_amd_decode_rows_batch_device_ragged")
+        raise capi.JpegLSError(rc, name)
     return errcs
 
 

@@ -42,6 +42,7 @@ SOURCES = [
     "host/misc_api.cpp",
     "host/batch_api.cpp",
     "host/batch_index.cpp",
+    "host/batch_bands.cpp",
     "host/batch_packed.cpp",
     "host/batch_ragged.cpp",
     "host/batch_budget.cpp",

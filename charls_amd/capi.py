@@ -529,3 +529,15 @@ def transcode_counters(lib: CharLSLibrary | None = None) -> tuple:
     n = L.charls_amd_transcode_counters(out, 4)
     assert n == 4
     return tuple(int(v) for v in out)
+
+
+def band_marker_counters(lib: CharLSLibrary | None = None) -> dict:
+    """charls_amd_band_marker_counters (part 2m): frames that took the marker route of batch.decode_rows_batch_ragged_markers,
+    intervals decoded on it, frames that fell back after starting it, launches it made; process-wide."""
+    L = (lib or load_product()).lib
+    L.charls_amd_band_marker_counters.argtypes = [C.POINTER(C.c_uint64), C.c_int32]
+    L.charls_amd_band_marker_counters.restype = C.c_int32
+    out = (C.c_uint64 * 4)()
+    n = L.charls_amd_band_marker_counters(out, 4)
+    assert n == 4
+    return dict(zip(("frames", "intervals", "fallback_frames", "launches"), (int(v) for v in out)))

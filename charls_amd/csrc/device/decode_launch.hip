@@ -379,6 +379,15 @@ void launch_decode_intervals(const ScanDesc& proto, const ScanDesc* d_descs, Sca
 }
 } // namespace
 
+void launch_find_restart_markers(const ScanDesc* d_descs, uint32_t* d_marks, uint32_t max_marks, uint32_t* d_counts, uint32_t count,
+                                 hipStream_t stream)
+{
+    if (count == 0)
+        return;
+    hipLaunchKernelGGL(interval::find_restart_markers, dim3(count), dim3(64), 0, stream, d_descs, d_marks, max_marks, d_counts);
+    hip_check(hipGetLastError());
+}
+
 // All `count` scans share proto's geometry and restart interval (salvage_launch_key).  The intervals of every scan are found
 // by their markers as far as these can be trusted, decoded as scans of their own by the ordinary decoders -- the exact decoder's
 // one launch settles what the speed path leaves undecided -- and judged; the rows of the intervals that are not kept are filled.

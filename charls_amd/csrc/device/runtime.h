@@ -112,6 +112,12 @@ uint64_t decode_launch_key(const ScanDesc& d) noexcept;
 void launch_decode(const ScanDesc& proto, const ScanDesc* d_descs, ScanResult* d_results, uint32_t count,
                    hipStream_t stream);
 
+// The marker walk of the restart-interval decoder on its own (restart_intervals_decode.hip: find_restart_markers), one
+// wavefront per scan: d_marks[i * max_marks + k] = where the 0xFF of scan i's k-th RSTm lies, from d_descs[i].stream;
+// d_counts[i] = the RSTm markers in front of the first other marker (0xFFFFFFFF: more than max_marks).  Nothing is decoded.
+void launch_find_restart_markers(const ScanDesc* d_descs, uint32_t* d_marks, uint32_t max_marks, uint32_t* d_counts, uint32_t count,
+                                 hipStream_t stream);
+
 // Salvage decode (salvage_intervals.hip; charls_amd.h part 2g): what launch_decode cannot decode whole, by restart intervals.
 // A scan qualifies when its intervals can be decoded as scans of their own; scans with equal keys share a launch (they have
 // the same geometry, height and restart interval).
@@ -195,6 +201,10 @@ DeviceBuffer& transcode_arena();
 // The calling thread's scratch frames of the index-only build (host/batch_index.cpp; charls_amd.h part 2l): the frames that get
 // no seek points are decoded into them, window by window, for their errc (a work area: counted and freed as the others).
 DeviceBuffer& index_scratch_arena();
+// The calling thread's edge intervals of charls_amd_decode_rows_batch_device_ragged_markers (host/batch_bands.cpp; charls_amd.h
+// part 2m): a restart interval that sticks out of a row band is decoded whole into it and its wanted rows are copied to the
+// band (a work area: counted and freed as the others).
+DeviceBuffer& band_edges_arena();
 // The calling thread's buffers of the seek-point index's batch calls (host/batch_index.cpp): seek points, work items, descs,
 // results, hash jobs (work areas: counted by work_area_bytes, freed by release_work_areas).
 constexpr int kSeekArenas = 6;

@@ -380,6 +380,11 @@ DeviceBuffer& index_scratch_arena()
     return work_buffer(WorkBuffer::index_scratch);
 }
 
+DeviceBuffer& band_edges_arena()
+{
+    return work_buffer(WorkBuffer::band_edges);
+}
+
 DeviceBuffer& seek_arena(int which)
 {
     return areas().buffers[static_cast<int>(WorkBuffer::seek_first) + which];

@@ -20,6 +20,7 @@ enum class WorkBuffer : int
     pack,     // staging slots of the packed batch encoder
     transcode, // decoded frames of a window of charls_amd_transcode_batch_device
     index_scratch, // scratch frames of the index-only build: the frames that get no seek points, a window at a time
+    band_edges, // the restart intervals that stick out of a row band (charls_amd.h part 2m), decoded whole beside it
     // restart-interval decode (launch_decode_intervals) and encode (launch_encode_intervals)
     marks,
     counts,

@@ -318,31 +318,6 @@ std::vector<charls_amd_frame_dest> slot_dests(uint32_t count, void* base, size_t
     return dests;
 }
 
-// The whole-call checks the calls of part 2l share: the tables, the destinations where there are any, the offsets.  Raises;
-// needs no device.  frame_count == 0 passes with any d_packed.
-void check_packed_index_call(uint32_t frame_count, const void* packed, const uint64_t* offsets, const uint64_t* sizes,
-                             const charls_amd_frame_dest* dests, const uint64_t* index_sizes, const charls_jpegls_errc* errcs)
-{
-    check_pointer(offsets);
-    check_pointer(sizes);
-    check_pointer(index_sizes);
-    check_pointer(errcs);
-    for (uint32_t f = 0; dests != nullptr && f < frame_count; ++f)
-    {
-        check_argument(dests[f].reserved == 0);
-        check_buffer(dests[f].d_pixels, dests[f].capacity_bytes);
-    }
-    if (frame_count == 0)
-        return;
-    check_pointer(packed);
-    for (uint32_t f = 0; f < frame_count; ++f)
-    {
-        uint64_t end;
-        if (__builtin_add_overflow(offsets[f], sizes[f], &end))
-            raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
-    }
-}
-
 // set_index for every frame that has one: parsed[i] (empty scans: none), errors to the frame.
 void parse_indexes(StreamWindows& s, const void* indexes, size_t index_pitch, const uint64_t* index_sizes, std::vector<SeekIndex>& parsed)
 {
@@ -378,6 +353,31 @@ struct Walk
 };
 
 } // namespace
+
+// The whole-call checks the calls of part 2l share: the tables, the destinations where there are any, the offsets.  Raises;
+// needs no device.  frame_count == 0 passes with any d_packed.
+void jls::check_packed_index_call(uint32_t frame_count, const void* packed, const uint64_t* offsets, const uint64_t* sizes,
+                                  const charls_amd_frame_dest* dests, const uint64_t* index_sizes, const charls_jpegls_errc* errcs)
+{
+    check_pointer(offsets);
+    check_pointer(sizes);
+    check_pointer(index_sizes);
+    check_pointer(errcs);
+    for (uint32_t f = 0; dests != nullptr && f < frame_count; ++f)
+    {
+        check_argument(dests[f].reserved == 0);
+        check_buffer(dests[f].d_pixels, dests[f].capacity_bytes);
+    }
+    if (frame_count == 0)
+        return;
+    check_pointer(packed);
+    for (uint32_t f = 0; f < frame_count; ++f)
+    {
+        uint64_t end;
+        if (__builtin_add_overflow(offsets[f], sizes[f], &end))
+            raise(CHARLS_JPEGLS_ERRC_INVALID_ARGUMENT_SIZE);
+    }
+}
 
 extern "C" charls_jpegls_errc charls_amd_index_size_bound(const charls_amd_codec_params* params, uint32_t lines_per_seek_point, size_t* bytes)
 try
@@ -1051,6 +1051,17 @@ void decode_bands(StreamWindows& s, const void* indexes, size_t index_pitch_byte
 }
 
 } // namespace
+
+// The body above for a caller in another unit (batch_bands.cpp: the frames its marker route leaves or gives back), with the
+// timings of a call of its own.
+void jls::decode_row_bands(StreamWindows& s, const void* indexes, size_t index_pitch_bytes, const uint64_t* index_sizes,
+                           const uint32_t* first_rows, const uint32_t* row_counts, const charls_amd_frame_dest* bands,
+                           charls_jpegls_errc* errcs)
+{
+    timings_begin();
+    decode_bands(s, indexes, index_pitch_bytes, index_sizes, first_rows, row_counts, bands, errcs);
+    timings_end();
+}
 
 extern "C" charls_jpegls_errc charls_amd_decode_rows_batch_device(uint32_t frame_count, const void* d_streams, size_t stream_pitch_bytes,
                                                                   const uint64_t* sizes, const void* indexes, size_t index_pitch_bytes,

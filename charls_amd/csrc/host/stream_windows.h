@@ -204,6 +204,15 @@ private:
 struct BatchDests;
 void check_ragged_dests(StreamWindows& win, const BatchDests& to);
 
+// charls_amd_decode_rows_batch_device_ragged behind its whole-call checks (batch_index.cpp: decode_bands), on frames whose
+// headers are read: every frame of `s` that is not done yet gets its band or its errc; errcs[i] = s.fr[i].errc for the others.
+void decode_row_bands(StreamWindows& s, const void* indexes, size_t index_pitch_bytes, const uint64_t* index_sizes,
+                      const uint32_t* first_rows, const uint32_t* row_counts, const charls_amd_frame_dest* bands,
+                      charls_jpegls_errc* errcs);
+// The same whole-call checks (batch_index.cpp: the tables, the destinations, the offsets); needs no device.
+void check_packed_index_call(uint32_t frame_count, const void* packed, const uint64_t* offsets, const uint64_t* sizes,
+                             const charls_amd_frame_dest* dests, const uint64_t* index_sizes, const charls_jpegls_errc* errcs);
+
 // The ordinary decoder launches for a set of scans of any geometry.  The device copies of the descriptors and results and
 // the line scratch live as long as the object: a caller that decodes in rounds reuses them.
 class DecodeLauncher

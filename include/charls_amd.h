@@ -1134,6 +1134,58 @@ CHARLS_AMD_API charls_jpegls_errc charls_amd_index_batch_host(
     void* indexes, size_t index_pitch_bytes, uint64_t* index_sizes, charls_amd_codec_params* params_out,
     charls_jpegls_errc* errcs);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Part 2m -- ROW BANDS THROUGH RESTART MARKERS.  A stream with restart intervals (written by the encoders on request, or
+ * by charls_amd_transcode_batch_device from a stream the caller holds) never has seek points, and
+ * charls_amd_decode_rows_batch_device_ragged decodes every such frame whole, one frame at a time, to copy a band out of it.
+ * A band of `rows` rows meets only the intervals j0 = first_row / Ri .. j1 = (first_row + rows - 1) / Ri of each scan, and an
+ * interval is a scan of its own.  charls_amd_decode_rows_batch_device_ragged_markers is that call, argument for argument --
+ * the same tables, the same whole-call checks, made before a device is asked for; frame_count == 0 is success --, with one
+ * more route for the frames that can take it.  None of the existing calls changes.
+ *
+ * A frame goes the MARKER ROUTE when its header was read and its band passed the stride and capacity checks of the ragged
+ * band call (a frame that fails them is written nowhere), its height does not come from DNL, index_sizes[f] == 0 or its
+ * index has no seek points, every scan has the first scan's parameters and a restart interval Ri with 0 < Ri < height, and
+ * every scan is one the interval-parallel decoder takes (not: lines beyond LDS, RESET = 256 m, 16-bit rows at an odd address
+ * or stride).  Every other frame is handed, unchanged, to the body of charls_amd_decode_rows_batch_device_ragged.
+ *
+ * On the route the restart markers of all such scans of the call are found in one launch per scan ordinal (the component
+ * scans of a planar frame each have their own markers; scan c + 1 is found behind the marker that ends scan c, nothing of
+ * scan c is decoded for that), their count must be ceil(height / Ri) - 1 and the markers up to the band must count
+ * RST0 .. RST7 cyclically.  The intervals the bands meet, of all frames, are decoded by the ordinary decoders in one launch per
+ * kernel specialisation: an interval that lies inside the band straight to its rows of bands[f], an interval that sticks out
+ * of it -- at most two per scan -- into one more work area of the calling thread (256-byte aligned per interval, within a
+ * quarter of what the thread's work areas may hold, counted by charls_amd_work_area_bytes, freed by
+ * charls_amd_release_work_areas), from which its wanted rows are copied.  Every band interval must end without error, decided,
+ * and -- but for the scan's last -- exactly at its marker.  A frame that fails any of this, or for whose edges there is no
+ * room, or when a per-call buffer of the route (descriptors, results, line scratch: not work areas) cannot be allocated,
+ * goes through the body of charls_amd_decode_rows_batch_device_ragged in the same call, which decodes it from the top
+ * and reports what the reference reports; rows of its band that the first attempt wrote are written again or left beside an
+ * errc, as that call leaves them.
+ *
+ * CONTRACT.  On a stream that decodes whole, bands and errcs are byte for byte those of
+ * charls_amd_decode_rows_batch_device_ragged.  The one deliberate difference: damage that lies in an interval the band does not
+ * meet (or behind the last scan), and that leaves the marker count and the marker numbers in front of the band intact, is not
+ * looked at -- the frame gets its band and errc 0, where the existing call fails the frame.  The indexed band path makes the
+ * same promise ("damage below it is not looked at"); a caller that wants the whole stream judged uses the existing call.
+ * Nothing is written outside a band's own rows, and one frame's failure never changes another frame's result.
+ *
+ * charls_amd_band_marker_counters, process-wide since the library was loaded: out[0] frames that took the marker route,
+ * out[1] intervals decoded on it, out[2] frames that fell back after starting it, out[3] launches the route made: one marker
+ * search per scan ordinal and one decode launch per kernel specialisation among the intervals (a launch of the exact decoder
+ * behind a speed path, for intervals that did not end cleanly there, is not counted).  Returns the number of values written
+ * (4 at most).  charls_amd_last_timings is that of the frames that
+ * went the existing way.
+ * Not done: part 1's decode_rows; the slot and host-memory forms; a sidecar of marker offsets, so that repeated bands of one
+ *   stream skip the marker walk; a row window inside the decode kernels, which would remove the edge copies; stopping the
+ *   marker walk at the marker the band needs (the walk has no per-scan parameter for it).
+ * ---------------------------------------------------------------------------------------------------------------- */
+CHARLS_AMD_API charls_jpegls_errc charls_amd_decode_rows_batch_device_ragged_markers(
+    uint32_t frame_count, const void* d_packed, const uint64_t* offsets, const uint64_t* sizes, const void* indexes,
+    size_t index_pitch_bytes, const uint64_t* index_sizes, const uint32_t* first_rows, const uint32_t* row_counts,
+    const charls_amd_frame_dest* bands, charls_jpegls_errc* errcs, void* hip_stream);
+CHARLS_AMD_API int32_t charls_amd_band_marker_counters(uint64_t* out, int32_t capacity);
+
 /* Engine selection for the lossless single-component encoder: 0 = automatic, 1 = force the one-wavefront-per-scan
  * kernel, 2 = force the parallel pipeline (returns invalid_argument when the scan is not eligible). Process-wide. */
 CHARLS_AMD_API charls_jpegls_errc charls_amd_set_encode_engine(int32_t engine);
